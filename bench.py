@@ -21,6 +21,14 @@
 # of queries whose TRUE nearest neighbor appears in the returned top-10;
 # ground truth by exact brute force on GPU. nprobe is swept to the smallest
 # value reaching 0.95.
+#
+# A plain run does only what the headline figure needs: build, operating
+# point, warm-up, the timed steps, the result line. --full adds the legs
+# that take runs of their own (served-path / graph-replay agreement checks,
+# scan-kernel roofline, CPU baseline); without it the result line carries
+# "roofline": null and "cpu_baseline": null. --dump-outputs DIR writes the
+# arrays the last timed step returned (seeded inputs: same arguments, same
+# queries and shard data on every run).
 import argparse
 import json
 import os
@@ -175,7 +183,16 @@ def main():
     ap.add_argument("--config", default="ivfpq_100m8_d768_m64",
                     choices=sorted(WORKLOADS))
     ap.add_argument("--target-recall", type=float, default=0.95)
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not "
+                         "need: served-path and graph-replay agreement "
+                         "checks, scan-kernel roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed "
+                         "step returned as DIR/distances.npy (float32) and "
+                         "DIR/ids.npy (float64 global ids)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="with --full: 0 skips the CPU-baseline leg")
     ap.add_argument("--cpu-sample-queries", type=int, default=256)
     ap.add_argument("--pq-precomputed", type=int, default=-1,
                     help="-1: workload default; 0/1 override")
@@ -321,15 +338,17 @@ def main():
     eng.nprobe = nprobe
     log(f"operating point: nprobe={nprobe} recall={recall:.4f}")
 
-    # one untimed pass through the FULL reference API (host arrays +
-    # metadata epilogue) to prove the served path and the timed path
+    # --full: one untimed pass through the FULL reference API (host arrays
+    # + metadata epilogue) to prove the served path and the timed path
     # agree — client.search wraps the same pipeline as search_dev
-    q4 = q[:4].cpu().numpy()
-    Dh, _meta_h = (client.search(q4, k, "bench")[:2])
-    Dd, _gid = run_search(nprobe, q[:4].contiguous())
-    # both carry the reference merge conventions (incl. quirk-2 negation)
-    assert np.allclose(np.asarray(Dh), Dd.cpu().numpy(), rtol=1e-6, atol=1e-6), \
-        "client.search diverged from the device serving step"
+    if args.full:
+        q4 = q[:4].cpu().numpy()
+        Dh, _meta_h = (client.search(q4, k, "bench")[:2])
+        Dd, _gid = run_search(nprobe, q[:4].contiguous())
+        # both carry the reference merge conventions (incl. quirk-2 negation)
+        assert np.allclose(np.asarray(Dh), Dd.cpu().numpy(),
+                           rtol=1e-6, atol=1e-6), \
+            "client.search diverged from the device serving step"
 
     # ---- timed region ----
     import torch.distributed as tdist
@@ -344,29 +363,36 @@ def main():
     # Serving-style step: capture the whole search step (coarse -> scan ->
     # merge) in a HIP graph and replay it — identical kernels and work,
     # zero host launch gaps (the 1M step is otherwise launch-bound).
-    # Verified below: one replay must reproduce the eager step bitwise.
-    # Multi-rank keeps the eager path (RCCL collectives stay outside
-    # graphs), so SCALE numbers are conservative.
+    # Verified under --full: one replay must reproduce the eager step
+    # bitwise. Multi-rank keeps the eager path (RCCL collectives stay
+    # outside graphs), so SCALE numbers are conservative.
     use_graph = world == 1 and args.graph
     if use_graph:
         try:
+            # one eager step right before capture, so no lazy allocation
+            # or first-use setup lands inside the captured region
             Dref, gref = run_search(nprobe, q)
             gobj = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gobj):
                 Dcap, gcap = run_search(nprobe, q)
-            gobj.replay()
+            gobj.replay()  # first replay uploads the graph: keep it untimed
             torch.cuda.synchronize()
-            assert torch.equal(gcap, gref) and torch.equal(Dcap, Dref), \
-                "graph replay diverged from eager step"
+            if args.full:
+                assert torch.equal(gcap, gref) and torch.equal(Dcap, Dref), \
+                    "graph replay diverged from eager step"
+            del Dref, gref
         except Exception as e:  # never let capture kill the bench
             log(f"graph capture unavailable ({e}); eager steps")
             use_graph = False
+    last = [None]  # what the most recent timed step returned (D, global ids)
     if use_graph:
+        last[0] = (Dcap, gcap)  # static graph outputs, rewritten per replay
+
         def step():
             gobj.replay()
     else:
         def step():
-            run_search(nprobe, q)
+            last[0] = run_search(nprobe, q)
     barrier()
     t0 = time.time()
     for _ in range(args.steps):
@@ -380,11 +406,75 @@ def main():
     ms_per_step = elapsed * 1000.0 / args.steps
     qps = cfg["nq"] * args.steps / elapsed
 
-    # ---- roofline leg (scan-kernel HIP-event timing, same workload) ----
+    # ---- --dump-outputs: what the last timed step handed its caller ----
+    # (merged distances + global ids of the whole query batch: nq x k each,
+    # far below any size worth sampling). ids go out as float64, exact for
+    # every id below 2^53.
+    if args.dump_outputs and rank == 0 and last[0] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        D_last, gid_last = last[0]
+        np.save(os.path.join(args.dump_outputs, "distances.npy"),
+                D_last.detach().cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "ids.npy"),
+                gid_last.detach().cpu().numpy().astype(np.float64))
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    roofline = None
+    cpu_baseline = None
+    if args.full:
+        roofline = roofline_leg(args, cfg, eng, nprobe,
+                                lambda: run_search(nprobe, q))
+        cpu_baseline = cpu_baseline_leg(args, cfg, spec, eng, nprobe, q, k,
+                                        rank, world)
+
+    if rank == 0:
+        out = {
+            "metric": "QPS at recall@10>=0.95 (IVFPQ sharded search)",
+            "value": qps,
+            "unit": "queries/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": args.config,
+                "n_per_shard": cfg["n"],
+                "dim": cfg["d"],
+                "nlist": cfg["nlist"],
+                "m": cfg["m"],
+                "k": k,
+                "nprobe": nprobe,
+                "recall_at_10": recall,
+                "batch": cfg["nq"],
+                "metric_space": "l2" if metric == 1 else "dot",
+                "coarse_dtype": "bf16" if cfg.get("coarse_bf16") else "f32",
+                "pq_lut": ("f16" if (cfg.get("pq_lut_f16", 0)
+                                     if args.pq_lut_f16 < 0
+                                     else args.pq_lut_f16)
+                           else "f32"),
+                "step_graph": bool(use_graph),
+                "serving_path": "IndexClient.search_dev",
+            },
+            # both legs run under --full only (null on a plain run)
+            "roofline": roofline,
+            "cpu_baseline": cpu_baseline,
+        }
+        print(json.dumps(out), flush=True)
+
+
+def roofline_leg(args, cfg, eng, nprobe, search_step):
+    """--full: scan-kernel HIP-event timing on the same workload."""
+    import torch
+
     eng.set_timing(True)
     eng.get_timing()  # reset
     for _ in range(3):
-        run_search(nprobe, q)
+        search_step()
     torch.cuda.synchronize()
     t = eng.get_timing()
     eng.set_timing(False)
@@ -445,7 +535,12 @@ def main():
                                            + t["merge_ms"] + t["lut_ms"],
                                            1e-9),
     }
+    return roofline
 
+
+def cpu_baseline_leg(args, cfg, spec, eng, nprobe, q, k, rank, world):
+    """--full: the CPU oracle scanning the engine's own lists (None when
+    the leg does not apply or --cpu-baseline 0)."""
     # ---- CPU baseline (rank 0, N=1): oracle scanning the SAME index ----
     cpu_baseline = None
     if rank == 0 and world == 1 and args.cpu_baseline:
@@ -501,44 +596,7 @@ def main():
                       f"{cpu_elapsed:.1f}s on host cores "
                       f"(os.cpu_count={os.cpu_count()})",
         }
-
-    if rank == 0:
-        out = {
-            "metric": "QPS at recall@10>=0.95 (IVFPQ sharded search)",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": args.config,
-                "n_per_shard": cfg["n"],
-                "dim": cfg["d"],
-                "nlist": cfg["nlist"],
-                "m": cfg["m"],
-                "k": k,
-                "nprobe": nprobe,
-                "recall_at_10": recall,
-                "batch": cfg["nq"],
-                "metric_space": "l2" if metric == 1 else "dot",
-                "coarse_dtype": "bf16" if cfg.get("coarse_bf16") else "f32",
-                "pq_lut": ("f16" if (cfg.get("pq_lut_f16", 0)
-                                     if args.pq_lut_f16 < 0
-                                     else args.pq_lut_f16)
-                           else "f32"),
-                "step_graph": bool(use_graph),
-                "serving_path": "IndexClient.search_dev",
-            },
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
-        }
-        print(json.dumps(out), flush=True)
+    return cpu_baseline
 
 
 if __name__ == "__main__":

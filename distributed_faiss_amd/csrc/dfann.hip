@@ -520,8 +520,21 @@ static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
   cn.ensure((size_t)kcent * 4);
   asg.ensure((size_t)nt * 4);
   bestv.ensure((size_t)nt * 4);
-  sums.ensure((size_t)kcent * d * 4);
+  sums.ensure((size_t)kcent * d * 8);  // 64-bit fixed point (k_centroid_accum)
   counts.ensure((size_t)kcent * 4);
+  // fixed-point scale 2^e with nt * max|x| * 2^e < 2^62 (frexp: max|x| <
+  // 2^ea, nt <= 2^en). bestv is free until the first assignment pass.
+  HIP_CHECK(hipMemsetAsync(bestv.p, 0, 4, stream));
+  hipLaunchKernelGGL(k_absmax, grid1d(nt * d), dim3(256), 0, stream, xt,
+                     (long long)(nt * d), bestv.as<unsigned>());
+  float absmax = 0.f;
+  HIP_CHECK(hipMemcpyAsync(&absmax, bestv.p, 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  int ea = 0, en = 0;
+  if (std::isfinite(absmax) && absmax > 0.f) std::frexp(absmax, &ea);
+  std::frexp((double)nt, &en);
+  const double acc_scale = std::ldexp(1.0, 62 - ea - en);
+  const double acc_inv_scale = std::ldexp(1.0, -(62 - ea - en));
   int64_t chunk = std::max<int64_t>(
       1, ((int64_t)(h ? h->ws_mb : 512) << 20) / ((int64_t)kcent * 4));
   chunk = std::min(chunk, nt);
@@ -551,16 +564,16 @@ static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
                          (long long)kcent, 0, bestv.as<float>() + s,
                          asg.as<int>() + s);
     }
-    HIP_CHECK(hipMemsetAsync(sums.p, 0, (size_t)kcent * d * 4, stream));
+    HIP_CHECK(hipMemsetAsync(sums.p, 0, (size_t)kcent * d * 8, stream));
     HIP_CHECK(hipMemsetAsync(counts.p, 0, (size_t)kcent * 4, stream));
     trace_point("kmeans:assign", stream);
     hipLaunchKernelGGL(k_centroid_accum, grid1d(nt * d), dim3(256), 0, stream,
-                       xt, asg.as<int>(), nt, d, sums.as<float>(),
-                       counts.as<int>());
+                       xt, asg.as<int>(), nt, d, acc_scale,
+                       sums.as<unsigned long long>(), counts.as<int>());
     trace_point("kmeans:accum", stream);
     hipLaunchKernelGGL(k_centroid_div, grid1d((int64_t)kcent * d), dim3(256), 0,
-                       stream, cent_out, sums.as<float>(), counts.as<int>(),
-                       (long long)kcent, d);
+                       stream, cent_out, sums.as<unsigned long long>(),
+                       counts.as<int>(), (long long)kcent, d, acc_inv_scale);
     // empty clusters: deterministic largest-donor split (== oracle)
     HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts.p, (size_t)kcent * 4,
                              hipMemcpyDeviceToHost, stream));

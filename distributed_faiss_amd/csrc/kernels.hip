@@ -2287,31 +2287,56 @@ extern "C" __global__ void k_subspace_slice(const float *__restrict__ in,
   }
 }
 
-// k-means accumulation (fp32 atomics; order nondeterminism documented)
+// max |x| of the training set, as the bit pattern of a non-negative float
+// (monotone as unsigned, so the atomicMax is order-independent). *out = 0
+// before launch. Sizes the fixed-point scale of k_centroid_accum.
+extern "C" __global__ void k_absmax(const float *__restrict__ x, long long total,
+                                    unsigned *__restrict__ out) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned m = 0u;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    unsigned e = __float_as_uint(fabsf(x[i]));
+    m = e > m ? e : m;
+  }
+  if (m) atomicMax(out, m);
+}
+
+// k-means accumulation in 64-bit FIXED POINT: x * 2^e rounded to an
+// integer, summed with integer atomics. Integer addition is associative,
+// so the sums — and with them the trained centroids — are bit-identical
+// from run to run whatever order the atomics land in (fp32 atomics were
+// not). The host picks e from max|x| and n so that n * max|x| * 2^e <
+// 2^62: no overflow, and a resolution of max|x| * n * 2^-62, far below
+// one fp32 ulp of any sum.
 extern "C" __global__ void k_centroid_accum(const float *__restrict__ x,
                                             const int *__restrict__ assign,
-                                            long long n, int d,
-                                            float *__restrict__ sums,
+                                            long long n, int d, double scale,
+                                            unsigned long long *__restrict__ sums,
                                             int *__restrict__ counts) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = n * d;
   for (; i < total; i += (long long)gridDim.x * blockDim.x) {
     long long r = i / d;
     int t = (int)(i % d);
-    atomicAdd(&sums[(long long)assign[r] * d + t], x[i]);
+    long long v = __double2ll_rn((double)x[i] * scale);
+    // two's-complement wrap makes the unsigned add a signed add
+    atomicAdd(&sums[(long long)assign[r] * d + t], (unsigned long long)v);
     if (t == 0) atomicAdd(&counts[assign[r]], 1);
   }
 }
 
 extern "C" __global__ void k_centroid_div(float *__restrict__ cent,
-                                          const float *__restrict__ sums,
+                                          const unsigned long long *__restrict__ sums,
                                           const int *__restrict__ counts,
-                                          long long kcent, int d) {
+                                          long long kcent, int d,
+                                          double inv_scale) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long total = kcent * d;
   for (; i < total; i += (long long)gridDim.x * blockDim.x) {
     long long c = i / d;
-    if (counts[c] > 0) cent[i] = sums[i] / (float)counts[c];
+    if (counts[c] > 0)
+      cent[i] = (float)((double)(long long)sums[i] * inv_scale /
+                        (double)counts[c]);
   }
 }
 

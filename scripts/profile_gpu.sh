@@ -17,7 +17,8 @@ OUT="$ROOT/gpurun_out/prof"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 
-BENCH_ARGS="${BENCH_ARGS:---steps 5 --warmup 2 --cpu-baseline 0}"
+# --full: pass 1 is compared with the roofline leg's HIP-event timing
+BENCH_ARGS="${BENCH_ARGS:---steps 5 --warmup 2 --full --cpu-baseline 0}"
 
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- \
     python "$ROOT/bench.py" $BENCH_ARGS > "$OUT/bench_trace.json" 2> "$OUT/trace.log"

@@ -30,7 +30,7 @@ for m in (64, 16):
 EOF
 echo "PERS_CHECK_RC=$?"
 
-B="python bench.py --steps 20 --warmup 5 --cpu-baseline 0"
+B="python bench.py --steps 20 --warmup 5 --full --cpu-baseline 0"
 # 1) persistent off (baseline with lut/scan split timing)
 DFANN_SCAN_PERS=0 $B > $O/r2s_pers0.json 2> $O/r2s_pers0.log; echo RC=$?
 # 2) persistent on (default blocks=2048)

@@ -628,3 +628,29 @@ def test_client_search_dev_matches_search(tmp_path):
         for i in range(6):
             for j in range(5):
                 assert Mh[i][j] == ("m", int(loc[i, j]))
+
+
+def test_training_is_bit_reproducible():
+    # k-means sums use integer (fixed-point) atomics, so two trainings of
+    # the same data + seed give the SAME centroids and codebooks bit for
+    # bit, whatever order the atomics land in. Sizes: several blocks per
+    # accumulation launch (20k x 48 elements), d no multiple of a tile,
+    # data offset from zero so positive and negative sums both occur.
+    rng = np.random.default_rng(5)
+    xb = (rng.standard_normal((20_000, 48)) * 3.0 + 0.5).astype(np.float32)
+    spec = {"type": "ivfpq", "dim": 48, "metric": 1, "nlist": 96, "m": 8,
+            "nbits": 8, "nprobe": 4, "seed": 77}
+    got = []
+    for _ in range(2):
+        eng = HipEngine(spec=spec)
+        eng.train(xb)
+        got.append((np.array(eng.get_centroids()), np.array(eng.get_codebooks())))
+    assert np.isfinite(got[0][0]).all() and np.isfinite(got[0][1]).all()
+    assert np.array_equal(got[0][0], got[1][0])
+    assert np.array_equal(got[0][1], got[1][1])
+    # and the means are right: every centroid is the fp32 mean of SOME
+    # non-empty subset, so it lies inside the data's bounding box (the
+    # empty-cluster split may push a centroid out by |v|/1024)
+    tol = float(np.abs(xb).max()) / 1024.0 + 1e-4
+    cent = got[0][0].reshape(-1, 48)
+    assert (cent >= xb.min(0) - tol).all() and (cent <= xb.max(0) + tol).all()
