@@ -271,15 +271,46 @@ class IndexClient:
         )
         return self._aggregate_results(results, topk, q_size, maximize_metric, return_embeddings)
 
+    def search_filtered(
+        self, query: np.ndarray, top_k: int, index_id: str,
+        filter_pos: int, filter_value
+    ) -> Tuple[np.ndarray, List[List[object]]]:
+        """Exact filtered search: the top_k nearest rows among those the
+        filter keeps (metadata m truthy, len(m) > filter_pos and
+        m[filter_pos] != filter_value — the predicate of
+        search_with_filter). Each shard applies the filter as an
+        allow-bitmap inside its scan kernels, so every query gets top_k
+        rows whenever that many allowed rows exist in the probed lists, at
+        any selectivity, and shards search (and gather) top_k rows, not
+        3 * top_k. Return format of search(): (nq, top_k) scores (negated
+        for dot, like search) and metadata with None at pads."""
+        q_size = query.shape[0]
+        maximize_metric: bool = self.cfg.metric == "dot"
+        if self.dist_mode:
+            return self._dist_search(
+                query, top_k, index_id, maximize_metric, False,
+                local_search=lambda: self.sub_indexes[0].search_filtered(
+                    index_id, query, top_k, filter_pos, filter_value))
+
+        def one(idx):
+            scores, _ids, meta, embs = idx.search_filtered(
+                index_id, query, top_k, filter_pos, filter_value)
+            return scores, meta, embs
+
+        results = self.pool.imap(one, self.sub_indexes)
+        return self._aggregate_results(results, top_k, q_size, maximize_metric, False)
+
     def _dist_search(self, query, topk, index_id, maximize_metric,
-                     return_embeddings):
+                     return_embeddings, local_search=None):
         """One-rank-per-shard fan-out: local search -> all-gather of
         (D, I) top-k over RCCL/gloo -> k-way merge (dfann_merge_topk on
         GPU) -> metadata mapped host-side from (shard, slot). Merge
         semantics identical to _aggregate_results (incl. quirk-2 dot
         negation and FLT_MAX pads that can win); metadata rides a
         collective object gather (the reference ships it in the RPC
-        responses, ref client.py:277-281)."""
+        responses, ref client.py:277-281). local_search: callable giving
+        this rank's (scores, ids, meta, embs) in place of search_full
+        (search_filtered)."""
         import torch
 
         from .dist import (
@@ -288,8 +319,11 @@ class IndexClient:
             merge_gathered_full,
         )
 
-        scores, ids, meta, embs = self.sub_indexes[0].search_full(
-            index_id, query, topk, return_embeddings)
+        if local_search is not None:
+            scores, ids, meta, embs = local_search()
+        else:
+            scores, ids, meta, embs = self.sub_indexes[0].search_full(
+                index_id, query, topk, return_embeddings)
         dev = "cuda" if torch.cuda.is_available() else "cpu"
         D = torch.as_tensor(np.ascontiguousarray(scores, dtype=np.float32),
                             device=dev)
@@ -340,6 +374,8 @@ class IndexClient:
         filter_value=None,
     ) -> Tuple[np.ndarray, List[List[object]]]:
         # reference client.py:213-263: over-fetch x3, host-side post-filter.
+        # (search_filtered is the exact path: same predicate, applied inside
+        # the scan kernels, full top_k at any selectivity.)
         # The over-fetch is clamped to the engine's k cap (512, see
         # include/dfann.h Limits) so a filtered search with top_k >= 171
         # degrades to a smaller candidate pool instead of raising where the

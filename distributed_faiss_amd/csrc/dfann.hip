@@ -333,6 +333,8 @@ struct dfann_index {
   DevBuf cent_bf16;
   DevBuf term2, term3_ws, qn_ws;  // PQ-L2 precomputed tables
   DevBuf pq_lut_ws;  // HBM ADC LUTs for the GLUT scan path
+  DevBuf filt_ws;    // filtered search: allow-bitmap in CSR-position space
+                     // (rebuilt by k_filter_id2pos on every filtered call)
 
   // timing
   bool timing = false;
@@ -1296,10 +1298,26 @@ static void coarse_impl(dfann_index *h, int64_t nq, const float *q, int nprobe,
   HIP_CHECK(hipGetLastError());
 }
 
+// allow != nullptr: filtered search. The caller's id-space bitmap is
+// translated to CSR-position space (k_filter_id2pos, on every call — a
+// cache keyed on the caller's pointer would go stale silently) and the
+// FILT twins of the scans test one bit per row. Needs a finalized CSR.
 static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                            int nprobe, const int32_t *probes,
                            const float *keys, int k, float *D, int64_t *I,
-                           hipStream_t stream) {
+                           hipStream_t stream,
+                           const uint32_t *allow = nullptr) {
+  const bool filt = allow != nullptr;
+  const unsigned *posbits = nullptr;
+  if (filt) {
+    // outside the scan timing events: not counted in scan_ms
+    int64_t waves = (h->ntotal + 63) / 64;
+    h->filt_ws.ensure((size_t)waves * 8);
+    hipLaunchKernelGGL(k_filter_id2pos, dim3((unsigned)((waves + 3) / 4)),
+                       dim3(256), 0, stream, allow, h->cr_ids.as<int64_t>(),
+                       (long long)h->ntotal, h->filt_ws.as<unsigned>());
+    posbits = h->filt_ws.as<unsigned>();
+  }
   // candidate arrays (sized after `fan` is chosen below)
   float *cand_d;
   unsigned *cand_p;
@@ -1308,6 +1326,13 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                const float *, const int *, const float *,
                const uint8_t *const *, const int64_t *, int, int, int, int,
                int, int, int, int, float *, unsigned *, int, int) = nullptr;
+  // filtered twin of `kern` (same arguments + the position bitmap); the
+  // env-gated experiment kernels have none and are ignored when filtering
+  void (*kern_f)(const float *, const float *, const float *, const float *,
+                 const float *, const int *, const float *,
+                 const uint8_t *const *, const int64_t *, int, int, int, int,
+                 int, int, int, int, float *, unsigned *, int, int,
+                 const unsigned *) = nullptr;
   bool ip = h->metric == M_IP;
   bool rk = use_regsel(k);
   switch (h->type) {
@@ -1315,17 +1340,23 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
       fam_floats = h->m * 256 + h->d;
       kern = rk ? (ip ? k_scan_pq_ip_rk : k_scan_pq_l2_rk)
                 : (ip ? k_scan_pq_ip : k_scan_pq_l2);
+      kern_f = rk ? (ip ? k_scan_pq_ip_rk_f : k_scan_pq_l2_rk_f)
+                  : (ip ? k_scan_pq_ip_f : k_scan_pq_l2_f);
       break;
     case T_IVFFLAT:
       fam_floats = h->d;
       kern = rk ? (ip ? k_scan_ivfflat_ip_rk : k_scan_ivfflat_l2_rk)
                 : (ip ? k_scan_ivfflat_ip : k_scan_ivfflat_l2);
+      kern_f = rk ? (ip ? k_scan_ivfflat_ip_rk_f : k_scan_ivfflat_l2_rk_f)
+                  : (ip ? k_scan_ivfflat_ip_f : k_scan_ivfflat_l2_f);
       break;
     case T_IVFSQ:
       if (h->sq8) {
         fam_floats = 2 * h->d;
         kern = rk ? (ip ? k_scan_sq8_ip_rk : k_scan_sq8_l2_rk)
                   : (ip ? k_scan_sq8_ip : k_scan_sq8_l2);
+        kern_f = rk ? (ip ? k_scan_sq8_ip_rk_f : k_scan_sq8_l2_rk_f)
+                    : (ip ? k_scan_sq8_ip_f : k_scan_sq8_l2_f);
         // DFANN_SCAN_NT=1: non-temporal code-row loads (A/B experiment)
         if (rk)
           if (const char *e = getenv("DFANN_SCAN_NT"))
@@ -1340,6 +1371,8 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
         fam_floats = h->d;
         kern = rk ? (ip ? k_scan_sqf_ip_rk : k_scan_sqf_l2_rk)
                   : (ip ? k_scan_sqf_ip : k_scan_sqf_l2);
+        kern_f = rk ? (ip ? k_scan_sqf_ip_rk_f : k_scan_sqf_l2_rk_f)
+                    : (ip ? k_scan_sqf_ip_f : k_scan_sqf_l2_f);
       }
       break;
     default:
@@ -1416,22 +1449,40 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
     if (h->timing) h->ev_end(el, stream, h->ev_lut);
     if (h->timing) e = h->ev_begin(stream);
     auto pk = rk ? k_scan_pq_l2_pre_rk : k_scan_pq_l2_pre;
-    hipLaunchKernelGGL(pk, dim3((unsigned)(nq * nprobe)), dim3(scan_bs), lds,
-                       stream, q, h->centroids.as<float>(),
-                       h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                       h->sq_scale.as<float>(), probes, keys,
-                       h->csr_arena.dev_table(stream),
-                       h->cr_off.as<int64_t>(),
-                       (int)nq, nprobe, h->d, h->m, h->dsub, k, h->stride,
-                       h->csr_arena.rlog,
-                       cand_d, cand_p, fam_floats, h->term2.as<float>(),
-                       h->term3_ws.as<float>(), h->qn_ws.as<float>());
+    auto pk_f = rk ? k_scan_pq_l2_pre_rk_f : k_scan_pq_l2_pre_f;
+    if (filt)
+      hipLaunchKernelGGL(pk_f, dim3((unsigned)(nq * nprobe)), dim3(scan_bs),
+                         lds, stream, q, h->centroids.as<float>(),
+                         h->codebooks.as<float>(), h->sq_vmin.as<float>(),
+                         h->sq_scale.as<float>(), probes, keys,
+                         h->csr_arena.dev_table(stream),
+                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
+                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
+                         cand_p, fam_floats, h->term2.as<float>(),
+                         h->term3_ws.as<float>(), h->qn_ws.as<float>(),
+                         posbits);
+    else
+      hipLaunchKernelGGL(pk, dim3((unsigned)(nq * nprobe)), dim3(scan_bs), lds,
+                         stream, q, h->centroids.as<float>(),
+                         h->codebooks.as<float>(), h->sq_vmin.as<float>(),
+                         h->sq_scale.as<float>(), probes, keys,
+                         h->csr_arena.dev_table(stream),
+                         h->cr_off.as<int64_t>(),
+                         (int)nq, nprobe, h->d, h->m, h->dsub, k, h->stride,
+                         h->csr_arena.rlog,
+                         cand_d, cand_p, fam_floats, h->term2.as<float>(),
+                         h->term3_ws.as<float>(), h->qn_ws.as<float>());
     if (h->timing) h->ev_end(e, stream, h->ev_scan);
   } else if (use_glut) {
     auto gk = lut_f16 ? (rk ? (ip ? k_scan_pq_ip_gh_rk : k_scan_pq_l2_gh_rk)
                             : (ip ? k_scan_pq_ip_gh : k_scan_pq_l2_gh))
                       : (rk ? (ip ? k_scan_pq_ip_g_rk : k_scan_pq_l2_g_rk)
                             : (ip ? k_scan_pq_ip_g : k_scan_pq_l2_g));
+    auto gk_f =
+        lut_f16 ? (rk ? (ip ? k_scan_pq_ip_gh_rk_f : k_scan_pq_l2_gh_rk_f)
+                      : (ip ? k_scan_pq_ip_gh_f : k_scan_pq_l2_gh_f))
+                : (rk ? (ip ? k_scan_pq_ip_g_rk_f : k_scan_pq_l2_g_rk_f)
+                      : (ip ? k_scan_pq_ip_g_f : k_scan_pq_l2_g_f));
     // chunk queries so the LUT buffer stays inside the budget (measured:
     // bigger chunks win — concurrency beats LLC residency)
     size_t row_b =
@@ -1480,7 +1531,7 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
       int pfn = 0;
       long long qpn_c = (long long)nqc * nprobe;
       const char *pers_env = getenv("DFANN_SCAN_PERS");
-      if (lut_f16 && rk && pers_env && atoi(pers_env) == 1) {
+      if (!filt && lut_f16 && rk && pers_env && atoi(pers_env) == 1) {
         int lut_u4 = h->m * 32;  // m*256 halves / 8 per uint4
         if (lut_u4 % (int)scan_bs == 0) {
           int cand = lut_u4 / (int)scan_bs;
@@ -1507,6 +1558,16 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                            h->m, h->dsub, k, h->stride, h->csr_arena.rlog,
                            cand_d + q0 * nprobe * k, cand_p + q0 * nprobe * k,
                            fam_floats, lutg);
+      } else if (filt) {
+        hipLaunchKernelGGL(gk_f, dim3((unsigned)(nqc * nprobe)), dim3(scan_bs),
+                           lds, stream, q + q0 * h->d, h->centroids.as<float>(),
+                           h->codebooks.as<float>(), h->sq_vmin.as<float>(),
+                           h->sq_scale.as<float>(), probes + q0 * nprobe,
+                           keys + q0 * nprobe, h->csr_arena.dev_table(stream),
+                           h->cr_off.as<int64_t>(), (int)nqc, nprobe, h->d,
+                           h->m, h->dsub, k, h->stride, h->csr_arena.rlog,
+                           cand_d + q0 * nprobe * k, cand_p + q0 * nprobe * k,
+                           fam_floats, lutg, posbits);
       } else {
         hipLaunchKernelGGL(gk, dim3((unsigned)(nqc * nprobe)), dim3(scan_bs),
                            lds, stream, q + q0 * h->d, h->centroids.as<float>(),
@@ -1522,13 +1583,24 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
     }
   } else {
     if (h->timing) e = h->ev_begin(stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nq * nprobe * fan)),
-                       dim3(scan_bs), lds, stream, q, h->centroids.as<float>(),
-                       h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                       h->sq_scale.as<float>(), probes, keys,
-                       h->csr_arena.dev_table(stream), h->cr_off.as<int64_t>(),
-                       (int)nq, nprobe, h->d, h->m, h->dsub, k, h->stride,
-                       h->csr_arena.rlog, cand_d, cand_p, fam_floats, fan);
+    if (filt)
+      hipLaunchKernelGGL(kern_f, dim3((unsigned)(nq * nprobe * fan)),
+                         dim3(scan_bs), lds, stream, q,
+                         h->centroids.as<float>(), h->codebooks.as<float>(),
+                         h->sq_vmin.as<float>(), h->sq_scale.as<float>(),
+                         probes, keys, h->csr_arena.dev_table(stream),
+                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
+                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
+                         cand_p, fam_floats, fan, posbits);
+    else
+      hipLaunchKernelGGL(kern, dim3((unsigned)(nq * nprobe * fan)),
+                         dim3(scan_bs), lds, stream, q,
+                         h->centroids.as<float>(), h->codebooks.as<float>(),
+                         h->sq_vmin.as<float>(), h->sq_scale.as<float>(),
+                         probes, keys, h->csr_arena.dev_table(stream),
+                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
+                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
+                         cand_p, fam_floats, fan);
     if (h->timing) h->ev_end(e, stream, h->ev_scan);
   }
   if (h->timing) {
@@ -1557,8 +1629,10 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   HIP_CHECK(hipGetLastError());
 }
 
+// allow != nullptr: filtered (id-space bitmap; flat ids are positions)
 static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
-                             float *D, int64_t *I, hipStream_t stream) {
+                             float *D, int64_t *I, hipStream_t stream,
+                             const uint32_t *allow = nullptr) {
   if (h->ntotal == 0) { pad_fill(h, nq, k, D, I, stream); return; }
   bool ip = h->metric == M_IP;
   const int64_t CH = std::min<int64_t>(65536, std::max<int64_t>(
@@ -1588,7 +1662,21 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
       gemm_keys(h, q + s * h->d, c, base, bn_rows, h->d, bn, qn + s,
                 ip ? 0 : 2, sc, stream);
       // winners layout: (nq, nch, k) — row stride nch*k
-      if (use_regsel(k)) {
+      if (allow) {
+        if (use_regsel(k))
+          hipLaunchKernelGGL(k_topk_rows_rk_f, dim3((unsigned)c), dim3(256),
+                             REGSEL_LDS_BYTES, stream, sc, c,
+                             (long long)bn_rows, (long long)bn_rows, k,
+                             (unsigned)b0, (long long)(nch * k),
+                             wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
+                             allow);
+        else
+          hipLaunchKernelGGL(k_topk_rows_f, dim3((unsigned)c), dim3(256),
+                             SEL_LDS_BYTES, stream, sc, c, (long long)bn_rows,
+                             (long long)bn_rows, k, (unsigned)b0,
+                             (long long)(nch * k), wd + (s * nch + ci) * k,
+                             wp + (s * nch + ci) * k, allow);
+      } else if (use_regsel(k)) {
         hipLaunchKernelGGL(k_topk_rows_rk, dim3((unsigned)c), dim3(256),
                            REGSEL_LDS_BYTES, stream, sc, c, (long long)bn_rows,
                            (long long)bn_rows, k, (unsigned)b0,
@@ -1617,12 +1705,28 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
   HIP_CHECK(hipGetLastError());
 }
 
+// shared argument checks of the two filtered entries
+static void check_filter(dfann_index *h, const uint32_t *allow,
+                         int64_t nbits) {
+  if (h->type == T_HNSW)
+    throw std::runtime_error("filtered search unsupported for hnswsq");
+  if (!allow) throw std::runtime_error("filtered search: null allow bitmap");
+  if (nbits < h->ntotal)
+    throw std::runtime_error(
+        "filtered search: allow bitmap covers " + std::to_string(nbits) +
+        " ids but the index holds " + std::to_string(h->ntotal));
+}
+
 static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
-                        float *D, int64_t *I, hipStream_t stream) {
+                        float *D, int64_t *I, hipStream_t stream,
+                        const uint32_t *allow = nullptr) {
   if (!h->trained) throw std::runtime_error("search on untrained index");
   if (k > 512) throw std::runtime_error("k > 512 unsupported");
   if (nq == 0) return;
-  if (h->type == T_FLAT) { flat_search_impl(h, nq, q, k, D, I, stream); return; }
+  if (h->type == T_FLAT) {
+    flat_search_impl(h, nq, q, k, D, I, stream, allow);
+    return;
+  }
   if (h->ntotal == 0) { pad_fill(h, nq, k, D, I, stream); return; }
   if (h->type == T_HNSW) { hnsw_search(h, nq, q, k, D, I, stream); return; }
   finalize_csr(h, stream);
@@ -1645,7 +1749,7 @@ static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
   int32_t *probes = pb.as<int32_t>();
   float *keys = reinterpret_cast<float *>(pb.as<uint8_t>() + (size_t)nq * nprobe * 4);
   coarse_impl(h, nq, q, nprobe, probes, keys, stream);
-  scan_and_merge(h, nq, q, nprobe, probes, keys, k, D, I, stream);
+  scan_and_merge(h, nq, q, nprobe, probes, keys, k, D, I, stream, allow);
 }
 
 // ---------------------------------------------------------------------------
@@ -1719,6 +1823,39 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   finalize_csr(h, (hipStream_t)stream);
   scan_and_merge(h, nq, q_dev, nprobe, probes_dev, keys_dev, k, D_dev, I_dev,
                  (hipStream_t)stream);
+  API_END
+}
+
+extern "C" int dfann_search_filtered(dfann_index *h, int64_t nq,
+                                     const float *q_dev, int k,
+                                     const uint32_t *allow_bits_dev,
+                                     int64_t nbits, float *D_dev,
+                                     int64_t *I_dev, dfann_stream stream) {
+  API_BEGIN
+  check_filter(h, allow_bits_dev, nbits);
+  search_impl(h, nq, q_dev, k, D_dev, I_dev, (hipStream_t)stream,
+              allow_bits_dev);
+  API_END
+}
+
+extern "C" int dfann_search_preassigned_filtered(
+    dfann_index *h, int64_t nq, const float *q_dev, int nprobe,
+    const int32_t *probes_dev, const float *keys_dev, int k,
+    const uint32_t *allow_bits_dev, int64_t nbits, float *D_dev,
+    int64_t *I_dev, dfann_stream stream) {
+  API_BEGIN
+  if (!h->trained || h->type == T_FLAT)
+    throw std::runtime_error("search_preassigned needs a trained IVF index");
+  check_filter(h, allow_bits_dev, nbits);
+  if (k > 512) throw std::runtime_error("k > 512 unsupported");
+  if (nq == 0) return 0;
+  if (h->ntotal == 0) {
+    pad_fill(h, nq, k, D_dev, I_dev, (hipStream_t)stream);
+    return 0;
+  }
+  finalize_csr(h, (hipStream_t)stream);
+  scan_and_merge(h, nq, q_dev, nprobe, probes_dev, keys_dev, k, D_dev, I_dev,
+                 (hipStream_t)stream, allow_bits_dev);
   API_END
 }
 

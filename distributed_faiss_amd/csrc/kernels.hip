@@ -60,6 +60,14 @@ __device__ __forceinline__ uint4 nt_load16(const void *p) {
   return c.u;
 }
 
+// allow-bitmap test (filtered search): uint32 words, bit i&31 of word
+// i>>5. Used with CSR positions (scan, bitmap from k_filter_id2pos) and
+// with arrival ids (flat top-k, the caller's bitmap as is).
+__device__ __forceinline__ bool pos_allowed(const unsigned *__restrict__ bits,
+                                            long long i) {
+  return (bits[i >> 5] >> (unsigned)(i & 31)) & 1u;
+}
+
 // ---------------------------------------------------------------------------
 // selection machinery: threshold-filtered append + block bitonic compact
 // LDS carve (16B aligned): float selD[SEL_CAP]; unsigned selP[SEL_CAP];
@@ -613,10 +621,24 @@ extern "C" __global__ __launch_bounds__(256) void k_rownorm(
 // out_d/out_p: (rows, k). grid.x = rows. dynamic LDS: SEL_LDS_BYTES.
 // ---------------------------------------------------------------------------
 
-extern "C" __global__ __launch_bounds__(256) void k_topk_rows(
+#define TOPK_TRY(V, POS)                                                       \
+  do {                                                                         \
+    unsigned p_ = (POS);                                                       \
+    if (!FILT || pos_allowed(allow, p_)) sel_try(s, V, p_);                    \
+  } while (0)
+#define TOPK_PUSH(V, POS)                                                      \
+  do {                                                                         \
+    unsigned p_ = (POS);                                                       \
+    if (!FILT || pos_allowed(allow, p_)) loc.push(V, p_);                      \
+  } while (0)
+// FILT: each offer is gated on the ID-space allow bit of pos = col + base
+// (flat ids are positions — no translation); rejected columns are skipped.
+template <bool FILT>
+__device__ __forceinline__ void topk_rows_body(
     const float *__restrict__ keys, long long rows, long long cols,
     long long ldk, int k, unsigned base, long long ldo,
-    float *__restrict__ out_d, unsigned *__restrict__ out_p) {
+    float *__restrict__ out_d, unsigned *__restrict__ out_p,
+    const unsigned *__restrict__ allow) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Sel s = sel_carve(smem);
   long long row = blockIdx.x;
@@ -639,25 +661,25 @@ extern "C" __global__ __launch_bounds__(256) void k_topk_rows(
       float4 v4 = v ? kp4[c4] : float4{0.f, 0.f, 0.f, 0.f};
       sel_guard(s, k, 2 * BS);
       if (v) {
-        sel_try(s, v4.x, (unsigned)(c4 * 4 + 0) + base);
-        sel_try(s, v4.y, (unsigned)(c4 * 4 + 1) + base);
+        TOPK_TRY(v4.x, (unsigned)(c4 * 4 + 0) + base);
+        TOPK_TRY(v4.y, (unsigned)(c4 * 4 + 1) + base);
       }
       sel_guard(s, k, 2 * BS);
       if (v) {
-        sel_try(s, v4.z, (unsigned)(c4 * 4 + 2) + base);
-        sel_try(s, v4.w, (unsigned)(c4 * 4 + 3) + base);
+        TOPK_TRY(v4.z, (unsigned)(c4 * 4 + 2) + base);
+        TOPK_TRY(v4.w, (unsigned)(c4 * 4 + 3) + base);
       }
     }
     sel_guard(s, k, BS);
     for (long long c = (c4n << 2) + threadIdx.x; c < cols; c += BS)
-      sel_try(s, kp[c], (unsigned)c + base);
+      TOPK_TRY(kp[c], (unsigned)c + base);
   } else {
     for (long long c0 = 0; c0 < cols; c0 += (long long)2 * BS) {
       sel_guard(s, k, 2 * BS);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         long long c = c0 + u * BS + threadIdx.x;
-        if (c < cols) sel_try(s, kp[c], (unsigned)c + base);
+        if (c < cols) TOPK_TRY(kp[c], (unsigned)c + base);
       }
     }
   }
@@ -672,10 +694,12 @@ extern "C" __global__ __launch_bounds__(256) void k_topk_rows(
 }
 
 // register-path top-k per row (k <= 16): no LDS buffer, no bitonic
-extern "C" __global__ __launch_bounds__(256) void k_topk_rows_rk(
+template <bool FILT>
+__device__ __forceinline__ void topk_rows_rk_body(
     const float *__restrict__ keys, long long rows, long long cols,
     long long ldk, int k, unsigned base, long long ldo,
-    float *__restrict__ out_d, unsigned *__restrict__ out_p) {
+    float *__restrict__ out_d, unsigned *__restrict__ out_p,
+    const unsigned *__restrict__ allow) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   long long row = blockIdx.x;
   if (row >= rows) return;
@@ -693,31 +717,68 @@ extern "C" __global__ __launch_bounds__(256) void k_topk_rows_rk(
     long long c4 = threadIdx.x;
     for (; c4 + BS < c4n; c4 += 2 * BS) {
       float4 v0 = kp4[c4], v1 = kp4[c4 + BS];
-      loc.push(v0.x, (unsigned)(c4 * 4 + 0) + base);
-      loc.push(v0.y, (unsigned)(c4 * 4 + 1) + base);
-      loc.push(v0.z, (unsigned)(c4 * 4 + 2) + base);
-      loc.push(v0.w, (unsigned)(c4 * 4 + 3) + base);
-      loc.push(v1.x, (unsigned)((c4 + BS) * 4 + 0) + base);
-      loc.push(v1.y, (unsigned)((c4 + BS) * 4 + 1) + base);
-      loc.push(v1.z, (unsigned)((c4 + BS) * 4 + 2) + base);
-      loc.push(v1.w, (unsigned)((c4 + BS) * 4 + 3) + base);
+      TOPK_PUSH(v0.x, (unsigned)(c4 * 4 + 0) + base);
+      TOPK_PUSH(v0.y, (unsigned)(c4 * 4 + 1) + base);
+      TOPK_PUSH(v0.z, (unsigned)(c4 * 4 + 2) + base);
+      TOPK_PUSH(v0.w, (unsigned)(c4 * 4 + 3) + base);
+      TOPK_PUSH(v1.x, (unsigned)((c4 + BS) * 4 + 0) + base);
+      TOPK_PUSH(v1.y, (unsigned)((c4 + BS) * 4 + 1) + base);
+      TOPK_PUSH(v1.z, (unsigned)((c4 + BS) * 4 + 2) + base);
+      TOPK_PUSH(v1.w, (unsigned)((c4 + BS) * 4 + 3) + base);
     }
     for (; c4 < c4n; c4 += BS) {
       float4 v0 = kp4[c4];
-      loc.push(v0.x, (unsigned)(c4 * 4 + 0) + base);
-      loc.push(v0.y, (unsigned)(c4 * 4 + 1) + base);
-      loc.push(v0.z, (unsigned)(c4 * 4 + 2) + base);
-      loc.push(v0.w, (unsigned)(c4 * 4 + 3) + base);
+      TOPK_PUSH(v0.x, (unsigned)(c4 * 4 + 0) + base);
+      TOPK_PUSH(v0.y, (unsigned)(c4 * 4 + 1) + base);
+      TOPK_PUSH(v0.z, (unsigned)(c4 * 4 + 2) + base);
+      TOPK_PUSH(v0.w, (unsigned)(c4 * 4 + 3) + base);
     }
     for (long long c = (c4n << 2) + threadIdx.x; c < cols; c += BS)
-      loc.push(kp[c], (unsigned)c + base);
+      TOPK_PUSH(kp[c], (unsigned)c + base);
   } else {
     for (long long c = threadIdx.x; c < cols; c += BS)
-      loc.push(kp[c], (unsigned)c + base);
+      TOPK_PUSH(kp[c], (unsigned)c + base);
   }
   __syncthreads();
   regtopk_block_extract<16>(loc, k, smem, out_d + row * ldo,
                             out_p + row * ldo);
+}
+
+#undef TOPK_TRY
+#undef TOPK_PUSH
+
+extern "C" __global__ __launch_bounds__(256) void k_topk_rows(
+    const float *__restrict__ keys, long long rows, long long cols,
+    long long ldk, int k, unsigned base, long long ldo,
+    float *__restrict__ out_d, unsigned *__restrict__ out_p) {
+  topk_rows_body<false>(keys, rows, cols, ldk, k, base, ldo, out_d, out_p,
+                        nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_topk_rows_f(
+    const float *__restrict__ keys, long long rows, long long cols,
+    long long ldk, int k, unsigned base, long long ldo,
+    float *__restrict__ out_d, unsigned *__restrict__ out_p,
+    const unsigned *__restrict__ allow) {
+  topk_rows_body<true>(keys, rows, cols, ldk, k, base, ldo, out_d, out_p,
+                       allow);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_topk_rows_rk(
+    const float *__restrict__ keys, long long rows, long long cols,
+    long long ldk, int k, unsigned base, long long ldo,
+    float *__restrict__ out_d, unsigned *__restrict__ out_p) {
+  topk_rows_rk_body<false>(keys, rows, cols, ldk, k, base, ldo, out_d, out_p,
+                           nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_topk_rows_rk_f(
+    const float *__restrict__ keys, long long rows, long long cols,
+    long long ldk, int k, unsigned base, long long ldo,
+    float *__restrict__ out_d, unsigned *__restrict__ out_p,
+    const unsigned *__restrict__ allow) {
+  topk_rows_rk_body<true>(keys, rows, cols, ldk, k, base, ldo, out_d, out_p,
+                          allow);
 }
 
 // ---------------------------------------------------------------------------
@@ -1150,7 +1211,8 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
 }
 
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE = false,
-          bool GLUT = false, bool L16 = false, bool NT = false, int UR = 4>
+          bool GLUT = false, bool L16 = false, bool NT = false, int UR = 4,
+          bool FILT = false>
 __device__ void ivf_scan_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
@@ -1162,7 +1224,14 @@ __device__ void ivf_scan_body(
     const float *__restrict__ term2 = nullptr,
     const float *__restrict__ term3 = nullptr,
     const float *__restrict__ qn = nullptr, int fan = 1,
-    const float *__restrict__ glut = nullptr) {
+    const float *__restrict__ glut = nullptr,
+    const unsigned *__restrict__ posbits = nullptr) {
+  // FILT: posbits is the allow-bitmap in CSR-POSITION space (built per
+  // call by k_filter_id2pos); a row whose bit is clear is never offered
+  // to the selector. The word load is issued next to the row's code load
+  // (independent of it), so the test adds no dependent round trip; the
+  // row's arithmetic is untouched, so surviving distances are bitwise
+  // the unfiltered ones.
   // fan > 1: each (query, probe) list is split into `fan` segments, one
   // block per segment — long-list tail imbalance at low block counts.
   // EXACT results: every segment's top-k contains the segment's global
@@ -1328,6 +1397,8 @@ __device__ void ivf_scan_body(
         long long pos = base + (long long)u * NG16 + grp;
         float dist = 0.f;
         bool valid = pos < s1;
+        bool allow = true;
+        if (FILT && valid) allow = pos_allowed(posbits, pos);
         if (valid) {
           const float *vp = reinterpret_cast<const float *>(slab_row(codes, rlog, pos, stride));
           float part = 0.f;
@@ -1343,7 +1414,7 @@ __device__ void ivf_scan_body(
           for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 16);
           dist = IS_IP ? -part : part;
         }
-        if (valid && sub == 0) {
+        if (valid && allow && sub == 0) {
           if (REGSEL) loc.push(dist, (unsigned)pos);
           else sel_try(s, dist, (unsigned)pos);
         }
@@ -1367,10 +1438,13 @@ __device__ void ivf_scan_body(
           // requests in flight per wave instead of 1 (latency hiding)
           uint4 wv4[UR];
           bool val4[UR];
+          bool ok4[UR];  // FILT: row valid AND allowed (else == val4)
 #pragma unroll
           for (int u = 0; u < UR; ++u) {
             long long pos = base + (long long)u * NG8 + grp;
             val4[u] = pos < s1;
+            ok4[u] = val4[u];
+            if (FILT && val4[u]) ok4[u] = pos_allowed(posbits, pos);
             int t0 = g8 * 16;
             // NT: non-temporal (evict-first) loads — the code stream is
             // read exactly once per step, keep it out of L2's way
@@ -1409,7 +1483,7 @@ __device__ void ivf_scan_body(
             part += __shfl_xor(part, 2, 8);
             part += __shfl_xor(part, 1, 8);
             float dist = IS_IP ? -(bias + part) : part;
-            if (val4[u] && g8 == 0) {
+            if (ok4[u] && g8 == 0) {
               if (REGSEL) loc.push(dist, (unsigned)pos);
               else sel_try(s, dist, (unsigned)pos);
             }
@@ -1419,6 +1493,8 @@ __device__ void ivf_scan_body(
           for (int u = 0; u < UR; ++u) {
             long long pos = base + (long long)u * NG8 + grp;
             bool valid = pos < s1;
+            bool allow = true;
+            if (FILT && valid) allow = pos_allowed(posbits, pos);
             float part = 0.f;
             if (valid) {
               const uint8_t *cp = slab_row(codes, rlog, pos, stride);
@@ -1446,7 +1522,7 @@ __device__ void ivf_scan_body(
             part += __shfl_xor(part, 2, 8);
             part += __shfl_xor(part, 1, 8);
             float dist = IS_IP ? -(bias + part) : part;
-            if (valid && g8 == 0) {
+            if (valid && allow && g8 == 0) {
               if (REGSEL) loc.push(dist, (unsigned)pos);
               else sel_try(s, dist, (unsigned)pos);
             }
@@ -1468,10 +1544,12 @@ __device__ void ivf_scan_body(
         if (u >= UROWS) break;
         long long pos = base + (long long)u * BS + threadIdx.x;
         if (pos < s1) {
+          bool allow = true;
+          if (FILT) allow = pos_allowed(posbits, pos);
           const uint8_t *cp = slab_row(codes, rlog, pos, stride);
           float acc = scan_row_dist<FAM, IS_IP, L16>(cp, fam, d, m);
           float dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
-          loc.push(dist, (unsigned)pos);
+          if (allow) loc.push(dist, (unsigned)pos);
         }
       }
     }
@@ -1483,10 +1561,12 @@ __device__ void ivf_scan_body(
       for (int u = 0; u < 2; ++u) {
         long long pos = base + (long long)u * BS + threadIdx.x;
         if (pos < s1) {
+          bool allow = true;
+          if (FILT) allow = pos_allowed(posbits, pos);
           const uint8_t *cp = slab_row(codes, rlog, pos, stride);
           float acc = scan_row_dist<FAM, IS_IP, L16>(cp, fam, d, m);
           float dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
-          sel_try(s, dist, (unsigned)pos);
+          if (allow) sel_try(s, dist, (unsigned)pos);
         }
       }
     }
@@ -1925,6 +2005,101 @@ INSTANTIATE_SCAN(k_scan_sq8_l2_rk, 2, false, true)
 INSTANTIATE_SCAN(k_scan_sq8_ip_rk, 2, true, true)
 INSTANTIATE_SCAN(k_scan_sqf_l2_rk, 3, false, true)
 INSTANTIATE_SCAN(k_scan_sqf_ip_rk, 3, true, true)
+
+// ---------------------------------------------------------------------------
+// filtered search (dfann_search_filtered): FILT=true twins of every scan
+// the dispatcher can pick from the spec — base (all families, fan),
+// PRE pair, GLUT g/gh set. Same signatures plus the trailing position
+// bitmap. The env-gated experiment kernels (nt / u8 / ghp) have no twin.
+// ---------------------------------------------------------------------------
+
+#define INSTANTIATE_SCAN_F(NAME, FAM, IS_IP, REGSEL)                           \
+  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
+      const float *q, const float *cent, const float *cb,                      \
+      const float *sq_vmin, const float *sq_scale, const int *probes,          \
+      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
+      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
+      float *cand_d, unsigned *cand_p, int fam_floats, int fan,                \
+      const unsigned *posbits) {                                               \
+    ivf_scan_body<FAM, IS_IP, REGSEL, false, false, false, false, 4, true>(    \
+        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
+        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
+        nullptr, nullptr, fan, nullptr, posbits);                              \
+  }
+INSTANTIATE_SCAN_F(k_scan_pq_l2_f, 0, false, false)
+INSTANTIATE_SCAN_F(k_scan_pq_ip_f, 0, true, false)
+INSTANTIATE_SCAN_F(k_scan_ivfflat_l2_f, 1, false, false)
+INSTANTIATE_SCAN_F(k_scan_ivfflat_ip_f, 1, true, false)
+INSTANTIATE_SCAN_F(k_scan_sq8_l2_f, 2, false, false)
+INSTANTIATE_SCAN_F(k_scan_sq8_ip_f, 2, true, false)
+INSTANTIATE_SCAN_F(k_scan_sqf_l2_f, 3, false, false)
+INSTANTIATE_SCAN_F(k_scan_sqf_ip_f, 3, true, false)
+INSTANTIATE_SCAN_F(k_scan_pq_l2_rk_f, 0, false, true)
+INSTANTIATE_SCAN_F(k_scan_pq_ip_rk_f, 0, true, true)
+INSTANTIATE_SCAN_F(k_scan_ivfflat_l2_rk_f, 1, false, true)
+INSTANTIATE_SCAN_F(k_scan_ivfflat_ip_rk_f, 1, true, true)
+INSTANTIATE_SCAN_F(k_scan_sq8_l2_rk_f, 2, false, true)
+INSTANTIATE_SCAN_F(k_scan_sq8_ip_rk_f, 2, true, true)
+INSTANTIATE_SCAN_F(k_scan_sqf_l2_rk_f, 3, false, true)
+INSTANTIATE_SCAN_F(k_scan_sqf_ip_rk_f, 3, true, true)
+
+#define INSTANTIATE_SCAN_PRE_F(NAME, REGSEL)                                   \
+  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
+      const float *q, const float *cent, const float *cb,                      \
+      const float *sq_vmin, const float *sq_scale, const int *probes,          \
+      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
+      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
+      float *cand_d, unsigned *cand_p, int fam_floats, const float *term2,     \
+      const float *term3, const float *qn, const unsigned *posbits) {          \
+    ivf_scan_body<0, false, REGSEL, true, false, false, false, 4, true>(       \
+        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
+        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, term2, term3, \
+        qn, 1, nullptr, posbits);                                              \
+  }
+INSTANTIATE_SCAN_PRE_F(k_scan_pq_l2_pre_f, false)
+INSTANTIATE_SCAN_PRE_F(k_scan_pq_l2_pre_rk_f, true)
+
+#define INSTANTIATE_SCAN_GLUT_F(NAME, IS_IP, REGSEL, L16)                      \
+  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
+      const float *q, const float *cent, const float *cb,                      \
+      const float *sq_vmin, const float *sq_scale, const int *probes,          \
+      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
+      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
+      float *cand_d, unsigned *cand_p, int fam_floats, const float *glut,      \
+      const unsigned *posbits) {                                               \
+    ivf_scan_body<0, IS_IP, REGSEL, false, true, L16, false, 4, true>(         \
+        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
+        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
+        nullptr, nullptr, 1, glut, posbits);                                   \
+  }
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_g_f, false, false, false)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_g_f, true, false, false)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_g_rk_f, false, true, false)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_g_rk_f, true, true, false)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_gh_f, false, false, true)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_f, true, false, true)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_gh_rk_f, false, true, true)
+INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_rk_f, true, true, true)
+
+// id-space allow-bitmap -> CSR-position-space bitmap: one thread per
+// position p, bit = allow[cr_ids[p]], packed with the 64-lane ballot;
+// lane 0 stores the wave's two words. The tail wave masks p >= ntotal to
+// 0, and waves wholly past ntotal store nothing, so posbits needs exactly
+// 2 * ceil(ntotal / 64) words. The scans then test one bit per row
+// instead of reading cr_ids[pos] (8 B next to a 16-B PQ code).
+extern "C" __global__ __launch_bounds__(256) void k_filter_id2pos(
+    const unsigned *__restrict__ allow, const int64_t *__restrict__ cr_ids,
+    long long ntotal, unsigned *__restrict__ posbits) {
+  long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bit = false;
+  if (p < ntotal) bit = pos_allowed(allow, cr_ids[p]);
+  unsigned long long b = __ballot(bit);
+  if ((threadIdx.x & 63) == 0 && p < ntotal) {
+    long long w = p >> 6;
+    posbits[2 * w] = (unsigned)b;
+    posbits[2 * w + 1] = (unsigned)(b >> 32);
+  }
+}
 
 // ---------------------------------------------------------------------------
 // merge scan candidates -> final (D, I) per query.

@@ -75,6 +75,12 @@ def load_lib():
                                              c.c_int, c.c_void_p, c.c_void_p,
                                              c.c_int, c.c_void_p, c.c_void_p,
                                              c.c_void_p]
+    lib.dfann_search_filtered.argtypes = [c.c_void_p, c.c_int64, c.c_void_p,
+                                          c.c_int, c.c_void_p, c.c_int64,
+                                          c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.dfann_search_preassigned_filtered.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
+        c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.dfann_set_nprobe.argtypes = [c.c_void_p, c.c_int]
     lib.dfann_ntotal.argtypes = [c.c_void_p]
     lib.dfann_ntotal.restype = c.c_int64
@@ -115,6 +121,27 @@ def _torch():
             "the product path has no CPU fallback"
         )
     return torch
+
+
+def pack_allow_bits(allow):
+    """bool mask over ids -> int32 bitmap words (bit i&31 of word i>>5,
+    little-endian bit order), zero-padded to whole words."""
+    allow = np.ascontiguousarray(allow, dtype=bool).reshape(-1)
+    packed = np.packbits(allow, bitorder="little")
+    pad = (-packed.shape[0]) % 4
+    if pad or packed.shape[0] == 0:
+        packed = np.concatenate(
+            [packed, np.zeros(pad if packed.shape[0] else 4, dtype=np.uint8)])
+    return packed.view("<u4").view(np.int32)
+
+
+class PackedFilter:
+    """Device-resident allow-bitmap: `bits` int32 cuda tensor of words,
+    `nbits` the number of ids covered."""
+
+    def __init__(self, bits, nbits):
+        self.bits = bits
+        self.nbits = int(nbits)
 
 
 class HipEngine:
@@ -254,6 +281,62 @@ class HipEngine:
         _check(self.lib, self.lib.dfann_search_preassigned(
             self.h, nq, ctypes.c_void_p(qt.data_ptr()), nprobe,
             ctypes.c_void_p(pt.data_ptr()), ctypes.c_void_p(kt.data_ptr()), k,
+            ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+            self._stream(torch)))
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- filtered search (allow-bitmap applied inside the scan kernels) ----
+
+    def pack_filter(self, allow):
+        """Upload a boolean allow-mask over arrival ids (length >= ntotal)
+        as the engine's bitmap: uint32 words, bit i&31 of word i>>5, padded
+        to whole words. Returns a PackedFilter for search_filtered* — pack
+        once when the same filter serves several searches."""
+        torch = _torch()
+        return PackedFilter(torch.as_tensor(pack_allow_bits(allow)).cuda(),
+                            int(np.asarray(allow).shape[0]))
+
+    def _packed(self, allow):
+        return allow if isinstance(allow, PackedFilter) else self.pack_filter(allow)
+
+    def search_filtered(self, q, k, allow):
+        """Exact top-k over the rows with allow[id] true. `allow`: numpy
+        bool array of length >= ntotal, or a PackedFilter."""
+        torch = _torch()
+        qt = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32)).cuda()
+        f = self._packed(allow)
+        D, I = self.search_filtered_dev(qt, k, f.bits, f.nbits)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def search_filtered_dev(self, qt, k, bits_t, nbits, D=None, I=None):
+        """Device-resident filtered search: bits_t is an int32 cuda tensor
+        holding the bitmap words, nbits the number of ids it covers."""
+        torch = _torch()
+        nq = qt.shape[0]
+        if D is None:
+            D = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+        if I is None:
+            I = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+        _check(self.lib, self.lib.dfann_search_filtered(
+            self.h, nq, ctypes.c_void_p(qt.data_ptr()), k,
+            ctypes.c_void_p(bits_t.data_ptr()), int(nbits),
+            ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+            self._stream(torch)))
+        return D, I
+
+    def search_preassigned_filtered(self, q, probes, keys, k, allow):
+        torch = _torch()
+        qt = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32)).cuda()
+        pt = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.int32)).cuda()
+        kt = torch.as_tensor(np.ascontiguousarray(keys, dtype=np.float32)).cuda()
+        f = self._packed(allow)
+        nq, nprobe = pt.shape
+        D = torch.empty((nq, k), dtype=torch.float32, device="cuda")
+        I = torch.empty((nq, k), dtype=torch.int64, device="cuda")
+        _check(self.lib, self.lib.dfann_search_preassigned_filtered(
+            self.h, nq, ctypes.c_void_p(qt.data_ptr()), nprobe,
+            ctypes.c_void_p(pt.data_ptr()), ctypes.c_void_p(kt.data_ptr()), k,
+            ctypes.c_void_p(f.bits.data_ptr()), f.nbits,
             ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
             self._stream(torch)))
         return D.cpu().numpy(), I.cpu().numpy()

@@ -56,6 +56,8 @@ def _default_provider():
 
 
 class Index:
+    FILTER_CACHE_SIZE = 8  # cached search_filtered bitmaps (LRU)
+
     def __init__(self, cfg: IndexCfg, provider=None):
         self.cfg = cfg
         self.provider = provider if provider is not None else _default_provider()
@@ -66,6 +68,11 @@ class Index:
         self.index_lock = threading.Lock()
         self.state = IndexState.NOT_TRAINED
         self.engine = None
+        # search_filtered: (filter_pos, filter_value) -> allow-mask entry,
+        # insertion-ordered LRU (guarded by _filter_lock, which is never
+        # held together with index_lock)
+        self._filter_cache = {}
+        self._filter_lock = threading.Lock()
 
         self.index_save_time = time.time()
         self.index_saved_size = 0
@@ -83,6 +90,8 @@ class Index:
         with self.index_lock:
             self.engine = None
             self.state = IndexState.NOT_TRAINED
+        with self._filter_lock:
+            self._filter_cache.clear()
 
     def add_batch(
         self,
@@ -204,6 +213,87 @@ class Index:
                 ]
                 for i in range(nq)
             ]
+
+    def search_filtered(
+        self, query_batch: np.ndarray, top_k: int, filter_pos: int, filter_value
+    ) -> Tuple[np.ndarray, np.ndarray, List[List[object]], None]:
+        """Exact top-k over the rows the reference's filter predicate keeps
+        (ref client.py:213-263 `_do_filter`): metadata `m` is truthy,
+        len(m) > filter_pos and m[filter_pos] != filter_value. The
+        predicate becomes an allow-bitmap over arrival ids that the engine
+        applies inside its scan kernels, so results are exact at any
+        selectivity and `top_k` stays the engine's k. Returns
+        (scores, indexes, meta, None), shaped like search_full.
+
+        The first use of a (filter_pos, filter_value) pair evaluates the
+        predicate over all ntotal metadata rows in Python — O(ntotal);
+        later calls reuse the cached bitmap and only evaluate rows added
+        since (ids are append-only). The cache holds the 8 most recently
+        used filters; unhashable filter values are not cached."""
+        query_batch = np.ascontiguousarray(query_batch, dtype=np.float32)
+        while True:
+            with self.index_lock:
+                if self.state != IndexState.TRAINED:
+                    raise RuntimeError(f"Server index is not trained. state: {self.state}")
+                engine = self.engine
+                if not hasattr(engine, "search_filtered"):
+                    raise NotImplementedError(
+                        f"engine {type(engine).__name__} has no search_filtered: "
+                        "exact filtered search needs the HIP engine "
+                        "(use search_with_filter for the over-fetch path)")
+                ntotal = engine.ntotal
+            # the bitmap is built OUTSIDE index_lock: it takes buffer_lock,
+            # and _maybe_save orders buffer_lock before index_lock
+            flt = self._filter_for(engine, ntotal, filter_pos, filter_value)
+            with self.index_lock:
+                if self.state != IndexState.TRAINED:
+                    raise RuntimeError(f"Server index is not trained. state: {self.state}")
+                if self.engine is engine and engine.ntotal == ntotal:
+                    scores, indexes = engine.search_filtered(query_batch, top_k, flt)
+                    break
+            # rows were added in between: extend the bitmap and retry
+        return scores, indexes, self.metadata_for(indexes), None
+
+    @staticmethod
+    def _filter_allows(m, filter_pos, filter_value) -> bool:
+        # the reference predicate, ref client.py:236-240
+        return bool(m) and len(m) > filter_pos and m[filter_pos] != filter_value
+
+    def _filter_for(self, engine, ntotal, filter_pos, filter_value):
+        """Allow-mask over ids [0, ntotal): cached per (filter_pos,
+        filter_value), extended by the tail when ntotal has grown, and
+        uploaded once per change when the engine can keep it
+        device-resident (pack_filter)."""
+        with self._filter_lock:
+            return self._filter_for_locked(engine, ntotal, filter_pos, filter_value)
+
+    def _filter_for_locked(self, engine, ntotal, filter_pos, filter_value):
+        try:
+            key = (filter_pos, filter_value)
+            hash(key)
+        except TypeError:
+            key = None
+        entry = self._filter_cache.pop(key, None) if key is not None else None
+        if entry is None or entry["n"] > ntotal or entry["engine"] is not engine:
+            entry = {"n": 0, "allow": np.zeros(0, dtype=bool), "packed": None,
+                     "engine": engine}
+        if entry["n"] < ntotal:
+            with self.buffer_lock:
+                tail = np.fromiter(
+                    (self._filter_allows(m, filter_pos, filter_value)
+                     for m in self.id_to_metadata[entry["n"]:ntotal]),
+                    dtype=bool, count=ntotal - entry["n"])
+            entry["allow"] = np.concatenate([entry["allow"], tail])
+            entry["n"] = ntotal
+            entry["packed"] = None
+        if entry["packed"] is None:
+            pack = getattr(engine, "pack_filter", None)
+            entry["packed"] = pack(entry["allow"]) if pack else entry["allow"]
+        if key is not None:
+            self._filter_cache[key] = entry  # most recently used last
+            while len(self._filter_cache) > self.FILTER_CACHE_SIZE:
+                self._filter_cache.pop(next(iter(self._filter_cache)))
+        return entry["packed"]
 
     def search_ids_dev(self, qt, top_k: int):
         """Device-resident search: (D, I) stay in HBM (torch cuda

@@ -156,6 +156,16 @@ class IndexServer:
         return index.search_full(query_batch, top_k=top_k,
                                  return_embeddings=return_embeddings)
 
+    def search_filtered(
+        self, index_id: str, query_batch: np.ndarray, top_k: int,
+        filter_pos: int, filter_value
+    ) -> Tuple:
+        """Exact filtered search (Index.search_filtered): (scores, ids,
+        meta, None), shaped like search_full."""
+        index = self._get_index(index_id)
+        return index.search_filtered(query_batch, top_k, filter_pos,
+                                     filter_value)
+
     def search_ids_dev(self, index_id: str, qt, top_k: int):
         """Device-resident (D, I) search — the distributed client's timed
         serving step (no metadata epilogue, results stay in HBM)."""

@@ -17,6 +17,9 @@
  *    I = -1 with D = +FLT_MAX (L2) / -FLT_MAX (IP).
  *  - ids are implicit arrival positions per index (reference quirk,
  *    SURVEY.md §2 item 9).
+ *  - filtered search (dfann_search_filtered,
+ *    dfann_search_preassigned_filtered) takes an allow-bitmap over those
+ *    ids and applies it inside the scan kernels.
  *
  * Limits (engine caps; the faiss-backed reference has none of these):
  *  - k (top-k) <= 512 everywhere (dfann_search*, dfann_merge_topk):
@@ -92,6 +95,23 @@ int dfann_search_preassigned(dfann_index *h, int64_t nq, const float *q_dev,
                              int nprobe, const int32_t *probes_dev,
                              const float *keys_dev, int k, float *D_dev,
                              int64_t *I_dev, dfann_stream stream);
+
+/* Exact top-k over the rows whose arrival id is set in allow_bits_dev
+ * (uint32 words, bit i&31 of word i>>5; nbits >= ntotal, extra bits
+ * ignored). Same conventions, caps and pads as dfann_search. Mirrors faiss
+ * SearchParameters.sel = IDSelectorBitmap; replaces the over-fetch +
+ * host post-filter of ref client.py:213-263. The bitmap is read during
+ * the call only (stream-ordered; nothing is cached across calls).
+ * Errors: nbits < ntotal; hnswsq ("filtered search unsupported for
+ * hnswsq" — beam search under a filter is a different algorithm). */
+int dfann_search_filtered(dfann_index *h, int64_t nq, const float *q_dev, int k,
+                          const uint32_t *allow_bits_dev, int64_t nbits,
+                          float *D_dev, int64_t *I_dev, dfann_stream stream);
+/* dfann_search_preassigned under the same filter. */
+int dfann_search_preassigned_filtered(dfann_index *h, int64_t nq,
+        const float *q_dev, int nprobe, const int32_t *probes_dev,
+        const float *keys_dev, int k, const uint32_t *allow_bits_dev,
+        int64_t nbits, float *D_dev, int64_t *I_dev, dfann_stream stream);
 
 /* --- knobs / introspection -------------------------------------------- */
 
