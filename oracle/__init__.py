@@ -38,6 +38,14 @@
 #     within-list scans; cross-list tie order in faiss is heap-order
 #     dependent and unpinned).
 #
+# fp16-LUT tier (spec "pq_lut_f16"): OracleIVFPQ rounds every
+# ADC table entry to IEEE half once (numpy float16: round-to-nearest-even,
+# gradual underflow), widens it back to fp32 and sums sequentially in fp32
+# exactly as the exact path does; the IP bias stays fp32. This DEFINES the
+# engine's fp16-LUT scan bit for bit (tests/test_gpu_dispatch_parity.py);
+# it is the engine's own table approximation (faiss GpuIndexIVFPQ
+# useFloat16LookupTables analogue), not a faiss-cpu behaviour.
+#
 # hnswsq tier (round 2): the SEARCH side is restated
 # op-for-op (core.OracleHNSWSearch) and runs over the ENGINE'S OWN dumped
 # graph — engine search results are bitwise equal to it

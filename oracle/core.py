@@ -121,6 +121,7 @@ def kmeans(
     seed: int = 1234,
     niter: int = 25,
     max_points_per_centroid: int = 256,
+    stats: dict = None,
 ):
     """Train k centroids. Returns (k, d) fp32 centroids.
 
@@ -128,6 +129,9 @@ def kmeans(
     (strided here — deterministic deviation), random init by seeded
     partial shuffle, assignment by the index metric, centroid = mean of
     assigned points, empty cluster takes a split of the largest cluster.
+
+    stats: optional dict; receives "empty_splits", the number of
+    empty-cluster splits over all iterations (parity tests assert 0).
     """
     x = np.ascontiguousarray(x, dtype=np.float32)
     n, d = x.shape
@@ -140,6 +144,8 @@ def kmeans(
         raise ValueError(f"kmeans: n={n} < k={k}")
     init = partial_shuffle_indices(n, k, seed)
     cent = x[init].copy()
+    if stats is not None:
+        stats["empty_splits"] = 0
     for _ in range(niter):
         assign = assign_batch(x, cent, metric)
         sums = np.zeros((k, d), dtype=np.float64)
@@ -150,6 +156,8 @@ def kmeans(
         # deterministic empty-cluster split: largest donor (lowest index on ties)
         empties = np.flatnonzero(~nonz)
         if empties.size:
+            if stats is not None:
+                stats["empty_splits"] += int(empties.size)
             counts_work = counts.copy()
             eps = np.float32(1.0 / 1024.0)
             for ci in empties:
@@ -287,6 +295,7 @@ class _OracleIVFBase(_OracleIndexBase):
         super().__init__(d, metric)
         self.nlist = int(nlist)
         self.seed = int(seed)
+        self.max_ppc = 256  # k-means subsample cap per centroid (spec "max_ppc")
         self.centroids = None  # (nlist, d) fp32
         self.list_ids = [np.empty(0, dtype=np.int64) for _ in range(int(nlist))]
 
@@ -367,7 +376,8 @@ class OracleIVFFlat(_OracleIVFBase):
         self.list_data = [np.empty((0, d), dtype=np.float32) for _ in range(self.nlist)]
 
     def train(self, x):
-        self.centroids = kmeans(x, self.nlist, self.metric, self.seed)
+        self.centroids = kmeans(x, self.nlist, self.metric, self.seed,
+                                max_points_per_centroid=self.max_ppc)
         self.is_trained = True
 
     def add(self, x):
@@ -440,17 +450,23 @@ class OracleIVFPQ(_OracleIVFBase):
         self.m = int(m)
         self.dsub = d // m
         self.codebooks = None
+        # spec "pq_lut_f16": every ADC table entry is rounded to IEEE half
+        # once (round-to-nearest-even, gradual underflow) and widened back
+        # before the fp32 sequential sum — the engine's fp16-LUT scan
+        self.lut_f16 = False
         self.list_codes = [np.empty((0, m), dtype=np.uint8) for _ in range(self.nlist)]
 
     def train(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
-        self.centroids = kmeans(x, self.nlist, self.metric, self.seed)
+        self.centroids = kmeans(x, self.nlist, self.metric, self.seed,
+                                max_points_per_centroid=self.max_ppc)
         assign = assign_batch(x, self.centroids, self.metric)
         resid = x - self.centroids[assign]
         cb = np.empty((self.m, 256, self.dsub), dtype=np.float32)
         for j in range(self.m):
             sub = resid[:, j * self.dsub : (j + 1) * self.dsub]
-            cb[j] = kmeans(sub, 256, METRIC_L2, self.seed + 1 + j)
+            cb[j] = kmeans(sub, 256, METRIC_L2, self.seed + 1 + j,
+                           max_points_per_centroid=self.max_ppc)
         self.codebooks = cb
         self.is_trained = True
 
@@ -515,6 +531,8 @@ class OracleIVFPQ(_OracleIVFBase):
         if codes.shape[0] == 0:
             return None
         lut, bias0 = self.build_lut(qi, li)
+        if self.lut_f16:
+            lut = lut.astype(np.float16).astype(np.float32)
         dist = adc_scan(lut, codes)
         if self.metric == METRIC_INNER_PRODUCT:
             dist = (bias0 if bias is None else bias) + dist
@@ -580,7 +598,8 @@ class OracleIVFSQ(_OracleIVFBase):
 
     def train(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
-        self.centroids = kmeans(x, self.nlist, self.metric, self.seed)
+        self.centroids = kmeans(x, self.nlist, self.metric, self.seed,
+                                max_points_per_centroid=self.max_ppc)
         if self.qtype == "8bit":
             assign = assign_batch(x, self.centroids, self.metric)
             resid = x - self.centroids[assign]
@@ -721,7 +740,7 @@ def make_oracle_engine(spec: dict):
     """Build an oracle index from the engine spec dict.
 
     spec keys: type (flat|ivf_flat|ivfpq|ivfsq), dim, metric (0|1), nlist,
-    m, nbits, sq_type, nprobe, seed.
+    m, nbits, sq_type, nprobe, seed, max_ppc, pq_lut_f16.
     """
     t = spec["type"]
     d = int(spec["dim"])
@@ -734,11 +753,14 @@ def make_oracle_engine(spec: dict):
     elif t == "ivfpq":
         eng = OracleIVFPQ(d, int(spec["nlist"]), int(spec["m"]), metric,
                           int(spec.get("nbits", 8)), seed)
+        eng.lut_f16 = int(spec.get("pq_lut_f16", 0)) != 0
     elif t == "ivfsq":
         eng = OracleIVFSQ(d, int(spec["nlist"]), metric, spec.get("sq_type", "fp16"), seed)
     else:
         raise ValueError(f"unknown engine type {t}")
     eng.nprobe = int(spec.get("nprobe", 1))
+    if t != "flat":
+        eng.max_ppc = int(spec.get("max_ppc", 256))
     eng.spec = dict(spec)
     return eng
 

@@ -256,3 +256,139 @@ def test_search_and_reconstruct_shapes():
     # reconstruction of the top hit is close to the true vector
     err = np.linalg.norm(R[0, 0] - xb[I[0, 0]]) / np.linalg.norm(xb[I[0, 0]])
     assert err < 0.7
+
+
+# ---------------------------------------------------------------------------
+# fp16-LUT option (spec "pq_lut_f16"): half-rounded ADC tables, fp32 sum
+# ---------------------------------------------------------------------------
+
+
+def _pq_pair(metric, d=12, m=4, nlist=3, n=90, seed=70):
+    """Exact and fp16-LUT oracle IVFPQ over the same artifacts and rows."""
+    rng = np.random.default_rng(seed)
+    cent = (rng.standard_normal((nlist, d)) * 4.0).astype(np.float32)
+    cb = rng.standard_normal((m, 256, d // m)).astype(np.float32)
+    xb = (cent[rng.integers(0, nlist, n)]
+          + rng.standard_normal((n, d))).astype(np.float32)
+    q = (cent[rng.integers(0, nlist, 5)]
+         + rng.standard_normal((5, d))).astype(np.float32)
+    out = []
+    for f16 in (0, 1):
+        spec = {"type": "ivfpq", "dim": d, "metric": metric, "nlist": nlist,
+                "m": m, "nprobe": nlist, "pq_lut_f16": f16}
+        orc = make_oracle_engine(spec)
+        assert orc.lut_f16 == bool(f16)
+        orc.centroids, orc.codebooks, orc.is_trained = cent, cb, True
+        orc.add(xb)
+        out.append(orc)
+    return out[0], out[1], q
+
+
+@pytest.mark.parametrize("metric", [IP, L2])
+def test_pq_lut_f16_distance_bound(metric):
+    # each of the m summed table entries moves by at most half a half-ulp,
+    # i.e. |entry| * 2^-11, so a distance moves by at most
+    # m * max|lut| * 2^-11 (the fp32 sums' own rounding is orders below)
+    exact, half, q = _pq_pair(metric)
+    for qi in q:
+        for li in range(exact.nlist):
+            lut, _ = exact.build_lut(qi, li)
+            assert np.abs(lut).max() < 32752  # half range: no overflow
+            de, ids_e = exact._scan_one(qi, li, None)
+            dh, ids_h = half._scan_one(qi, li, None)
+            np.testing.assert_array_equal(ids_e, ids_h)
+            bound = exact.m * float(np.abs(lut).max()) * 2.0 ** -11
+            assert np.abs(de.astype(np.float64) - dh).max() <= bound
+    # the option changes values: not a no-op
+    De, _ = exact.search(q, 10)
+    Dh, _ = half.search(q, 10)
+    assert not np.array_equal(De, Dh)
+
+
+@pytest.mark.parametrize("metric", [IP, L2])
+def test_pq_lut_f16_hand_restatement(metric):
+    # 2 subspaces restated by hand: table entry (sequential t, fp32) ->
+    # half -> fp32, then acc = (0 + e0) + e1 in fp32, IP bias added in
+    # fp32 in front. Must equal the option's output BITWISE.
+    exact, half, q = _pq_pair(metric, d=6, m=2, nlist=2, n=40, seed=71)
+    cb, dsub = half.codebooks, 3
+    for qi in q:
+        for li in range(2):
+            codes = half.list_codes[li]
+            got, _ = half._scan_one(qi, li, None)
+            want = np.empty(codes.shape[0], np.float32)
+            for r, code in enumerate(codes):
+                acc = np.float32(0.0)
+                for j in range(2):
+                    e = np.float32(0.0)
+                    for t in range(dsub):
+                        w = cb[j][code[j]][t]
+                        if metric == L2:
+                            diff = np.float32(
+                                np.float32(qi[j * dsub + t]
+                                           - half.centroids[li][j * dsub + t])
+                                - w)
+                            e = np.float32(e + np.float32(diff * diff))
+                        else:
+                            e = np.float32(
+                                e + np.float32(qi[j * dsub + t] * w))
+                    acc = np.float32(acc + np.float32(np.float16(e)))
+                if metric == IP:
+                    bias = np.float32(0.0)
+                    for t in range(6):
+                        bias = np.float32(
+                            bias + np.float32(qi[t] * half.centroids[li][t]))
+                    acc = np.float32(bias + acc)
+                want[r] = acc
+            np.testing.assert_array_equal(got, want)
+
+
+def test_pq_lut_f16_half_subnormal_is_gradual():
+    # an entry below the smallest normal half (2^-14) keeps its leading
+    # bits (gradual underflow), it is not flushed to zero
+    v = np.array([2.0 ** -16 * 1.5, 2.0 ** -24, 2.0 ** -26], np.float32)
+    h = v.astype(np.float16).astype(np.float32)
+    np.testing.assert_array_equal(
+        h, np.array([2.0 ** -16 * 1.5, 2.0 ** -24, 0.0], np.float32))
+
+
+def test_kmeans_reports_empty_splits():
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((200, 4)).astype(np.float32)
+    st = {}
+    kmeans(x, 4, L2, seed=1, stats=st)
+    assert st["empty_splits"] == 0
+    # 3 distinct points, 5 centroids: some cluster is empty every iteration
+    y = np.repeat(np.eye(3, 4, dtype=np.float32), 4, axis=0)
+    kmeans(y, 5, L2, seed=1, stats=st)
+    assert st["empty_splits"] > 0
+
+
+def test_spec_max_ppc_caps_the_kmeans_subsample():
+    # spec "max_ppc" (the engine's k-means subsample cap per centroid):
+    # 400 rows, 4 lists, cap 4*16 = 64 -> training sees the strided 64
+    x = _data(400, 6, seed=9)
+    spec = {"type": "ivfsq", "dim": 6, "metric": L2, "nlist": 4,
+            "sq_type": "8bit", "seed": 5, "max_ppc": 16}
+    orc = make_oracle_engine(spec)
+    assert orc.max_ppc == 16
+    orc.train(x)
+    sel = (np.arange(64) * 400) // 64
+    np.testing.assert_array_equal(
+        orc.centroids, kmeans(x[sel], 4, L2, 5))
+    np.testing.assert_array_equal(
+        orc.centroids, kmeans(x, 4, L2, 5, max_points_per_centroid=16))
+    dflt = make_oracle_engine({k: v for k, v in spec.items() if k != "max_ppc"})
+    assert dflt.max_ppc == 256
+    dflt.train(x)
+    assert not np.array_equal(dflt.centroids, orc.centroids)
+    # PQ codebooks train under the same cap, as in the engine
+    y = _data(600, 4, seed=10)
+    pq = make_oracle_engine({"type": "ivfpq", "dim": 4, "metric": L2,
+                             "nlist": 2, "m": 2, "seed": 5, "max_ppc": 2})
+    pq.train(y)
+    resid = y - pq.centroids[
+        np.argmin(pairwise_scores(y, pq.centroids, L2), axis=1)]
+    np.testing.assert_array_equal(
+        pq.codebooks[1],
+        kmeans(resid[:, 2:], 256, L2, 5 + 1 + 1, max_points_per_centroid=2))
