@@ -664,6 +664,12 @@ static dfann_index *create_from_spec(const std::string &js) {
     if (h->metric != M_L2)
       { delete h; throw std::runtime_error("hnswsq requires L2 (ref index.py:52)"); }
     if (h->m <= 0) h->m = 128;  // reference store_n default
+    if (h->m < 2) {
+      // the level draw uses mL = 1/ln(M): M = 1 has no level distribution
+      delete h;
+      throw std::runtime_error(
+          "hnswsq store_n < 2 unsupported (level draw needs 1/ln(M))");
+    }
     if (h->m > 256) {
       delete h;
       throw std::runtime_error(
@@ -994,8 +1000,8 @@ static void finalize_csr(dfann_index *h, hipStream_t stream) {
 // HNSW host orchestration (type "hnswsq")
 // ---------------------------------------------------------------------------
 
-// deterministic level draw (splitmix64; clamped). The oracle does not
-// replicate this (graph parity is via the engine's own dump).
+// deterministic level draw (splitmix64; clamped). Restated by the oracle
+// (oracle/hnsw.py hnsw_draw_level); M >= 2 is enforced at create.
 static int hnsw_draw_level(uint64_t seed, int64_t id, int M) {
   SplitMix64 rng(seed ^ (uint64_t)(id * 0x9E3779B97F4A7C15ULL + 0x51ED2701ULL));
   double u = ((double)(rng.next() >> 11) + 1.0) * (1.0 / 9007199254740992.0);

@@ -12,16 +12,18 @@
 //    ((c1-c2)*scale)^2 per dim.
 //  * build: BATCHED wave insertion — wave w inserts its points in
 //    parallel over a frozen snapshot of the graph after wave w-1 (one
-//    block per point), then reverse links are applied in (dst, src)
-//    SORTED order — the whole build is DETERMINISTIC given (data, seed,
-//    wave schedule), unlike an atomics-ordered build. Differs from
-//    faiss's strictly sequential insertion (documented deviation; graph
-//    quality is gated by recall property tests).
+//    block per point), then reverse links are applied in (dst, level,
+//    src) SORTED order — the whole build is DETERMINISTIC given (data,
+//    seed, wave schedule), unlike an atomics-ordered build, and is
+//    restated op-for-op by the oracle (oracle/hnsw.py: the graph is
+//    pinned bit for bit). Differs from faiss's strictly sequential
+//    insertion (documented deviation; graph quality is gated by recall
+//    property tests).
 //  * beam search: the Sel threshold+bitonic machinery keeps the top-ef
 //    frontier; expanded entries are flagged in bit 31 of the packed id;
-//    the visited set is an 8192-slot open-addressing hash in LDS
-//    (probe cap 32; a full cluster treats the id as visited — a
-//    deterministic, oracle-replicable approximation).
+//    the visited set is a 16384-slot open-addressing hash in LDS
+//    (HNSW_HASH; probe cap 64, HNSW_PROBES; a full cluster treats the id
+//    as visited — a deterministic, oracle-replicable approximation).
 //  * levels: splitmix64(seed ^ id) -> geometric with mL = 1/ln(M),
 //    clamped to HNSW_MAXL. Level-0 degree cap 2M, upper levels M
 //    (faiss conventions).
@@ -542,7 +544,14 @@ extern "C" __global__ __launch_bounds__(256) void k_hnsw_apply(
   // (dist, id) with a simple block bitonic over 1024 padded entries,
   // then shrink-select up to cap
   int total = old_cnt + inc;
-  if (total > 1024) total = 1024;  // defensive; cap + M*? never exceeds
+  // REACHABLE: the refine pass is one wave of up to 4096 points, and with
+  // duplicate vectors every point proposes the same lowest-id neighbour,
+  // so one run can bring more than 1024 - old_cnt requests. Only the
+  // first 1024 candidates are considered: the existing links, then the
+  // incoming sources in ascending id (the run is sorted by src) — the
+  // largest src ids are dropped. Deterministic and in bounds; the oracle
+  // mirrors it and tests/test_gpu_hnsw_build.py reaches it.
+  if (total > 1024) total = 1024;
   int g8 = threadIdx.x & 7, grp = threadIdx.x >> 3;
   const int NG = blockDim.x >> 3;
   for (int c0 = 0; c0 < total; c0 += NG) {

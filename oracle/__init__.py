@@ -46,14 +46,18 @@
 # it is the engine's own table approximation (faiss GpuIndexIVFPQ
 # useFloat16LookupTables analogue), not a faiss-cpu behaviour.
 #
-# hnswsq tier (round 2): the SEARCH side is restated
-# op-for-op (core.OracleHNSWSearch) and runs over the ENGINE'S OWN dumped
-# graph — engine search results are bitwise equal to it
-# (tests/test_hnsw.py). The BUILD side is NOT restated: the engine's
-# batched wave insertion is a documented deviation from faiss's
-# sequential insertion (parity unpinned there by construction); the
-# build's pinned contracts are determinism (identical graph dumps) and
-# recall property gates.
+# hnswsq tier (oracle/hnsw.py): BOTH sides are restated
+# op-for-op. core.OracleHNSWSearch mirrors k_hnsw_search over any graph of
+# the hnsw_dump layout; core.OracleHNSWBuild mirrors the build — host level
+# draws and wave schedule, k_hnsw_insert over the frozen snapshot, the
+# (dst, level, src)-sorted reverse-link merge of k_hnsw_apply (fast path,
+# over-cap prune, truncation of a run to 1024 candidates), the entry
+# update and the refine pass. The engine's graph dump and its search
+# results over that graph are bitwise equal to the oracle's
+# (tests/test_hnsw.py, tests/test_gpu_hnsw_build.py). The batched wave
+# insertion itself is a documented deviation from faiss's sequential
+# insertion (parity with faiss unpinned there by construction; graph
+# quality is held by the recall property gate).
 
 from .core import (  # noqa: F401
     METRIC_INNER_PRODUCT,
@@ -70,4 +74,6 @@ from .core import (  # noqa: F401
     load_oracle_engine,
     OracleProvider,
     aggregate_results,
+    OracleHNSWSearch,
+    OracleHNSWBuild,
 )

@@ -4,8 +4,10 @@
 #  * search: BIT-EXACT vs the oracle restatement over the engine's own
 #    dumped graph (OracleHNSWSearch mirrors k_hnsw_search op-for-op).
 #  * build: deterministic (same data + seed -> identical graph dump) and
-#    recall-gated (the batched wave insertion is a documented deviation
-#    from faiss's sequential insertion — graph quality is the contract).
+#    recall-gated here (the batched wave insertion is a documented
+#    deviation from faiss's sequential insertion); the graph itself is
+#    pinned bit for bit against the oracle's build restatement in
+#    tests/test_gpu_hnsw_build.py.
 #  * persistence: save/load -> identical graph + results.
 import os
 import sys
