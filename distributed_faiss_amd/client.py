@@ -475,6 +475,10 @@ class IndexClient:
     def set_nprobe(self, index_id: str, nprobe: int):
         return self.pool.map(lambda idx: idx.set_nprobe(index_id, nprobe), self.sub_indexes)
 
+    def set_k_factor(self, index_id: str, k_factor: float):
+        return self.pool.map(
+            lambda idx: idx.set_k_factor(index_id, k_factor), self.sub_indexes)
+
     def get_state(self, index_id: str) -> IndexState:
         if self.dist_mode:
             from .dist import all_gather_object

@@ -92,6 +92,13 @@ static long long json_int(const std::string &js, const char *key, long long dflt
   return atoll(v.c_str());
 }
 
+// float-valued keys ("k_factor": 1.6); json_int would truncate them
+static double json_float(const std::string &js, const char *key, double dflt) {
+  std::string v;
+  if (!json_find(js, key, v) || v.empty()) return dflt;
+  return atof(v.c_str());
+}
+
 static std::string json_str(const std::string &js, const char *key,
                             const char *dflt) {
   std::string v;
@@ -153,6 +160,8 @@ struct SlabArena {
   int64_t rows = 0;             // rows in use (bump)
   DevBuf table;                 // device copy of `slabs`
   bool table_dirty = true;
+  bool zero_new = false;        // zero-fill fresh slabs (refine store: pad
+                                // bytes of a row are part of its contract)
 
   void init(int stride_, size_t target_slab_bytes = (size_t)512 << 20) {
     reset();
@@ -167,6 +176,11 @@ struct SlabArena {
     while (slabs.size() < need) {
       void *p = nullptr;
       HIP_CHECK(hipMalloc(&p, slab_bytes()));
+      if (zero_new) {
+        // null-stream memset: drained before any stream writes rows
+        HIP_CHECK(hipMemset(p, 0, slab_bytes()));
+        HIP_CHECK(hipStreamSynchronize(0));
+      }
       slabs.push_back(p);
       table_dirty = true;
     }
@@ -335,6 +349,12 @@ struct dfann_index {
   DevBuf pq_lut_ws;  // HBM ADC LUTs for the GLUT scan path
   DevBuf filt_ws;    // filtered search: allow-bitmap in CSR-position space
                      // (rebuilt by k_filter_id2pos on every filtered call)
+  // refine stage: raw rows in arrival order (row i = id i),
+  // never rebuilt or moved; the base stage searches k' into rf_D / rf_I
+  int refine = 0;          // spec "refine": 0 off, 1 fp32, 2 fp16
+  double k_factor = 1.0;   // spec "k_factor" / dfann_set_k_factor
+  SlabArena refine_arena;
+  DevBuf rf_D, rf_I;
 
   // timing
   bool timing = false;
@@ -693,6 +713,39 @@ static dfann_index *create_from_spec(const std::string &js) {
   h->csr_arena.init(h->stride, (size_t)64 << 20);
   h->pend_arena.init(h->stride, (size_t)64 << 20);
   if (h->nlist > 0) h->h_off.assign(h->nlist + 1, 0);
+  // refine stage (faiss IndexRefineFlat / IndexRefine(SQfp16))
+  std::string rf = json_str(js, "refine", "");
+  if (!rf.empty()) {
+    if (rf == "fp32") h->refine = 1;
+    else if (rf == "fp16") h->refine = 2;
+    else {
+      delete h;
+      throw std::runtime_error("unknown refine codec '" + rf +
+                               "' (supported: fp32, fp16)");
+    }
+    if (h->type != T_IVFPQ && h->type != T_IVFSQ) {
+      delete h;
+      throw std::runtime_error("refine unsupported for index type '" + t +
+                               "' (supported bases: ivfpq, ivfsq)");
+    }
+    h->k_factor = json_float(js, "k_factor", 1.0);
+    if (!(h->k_factor >= 1.0)) {
+      delete h;
+      throw std::runtime_error("k_factor must be >= 1");
+    }
+    if (REFINE_LDS_BYTES(h->d) > 64 * 1024) {
+      delete h;
+      throw std::runtime_error("refine: dim too large for the query stage");
+    }
+    int slab_mb = (int)json_int(js, "refine_slab_mb", 64);
+    if (slab_mb < 1) slab_mb = 1;
+    h->refine_arena.init(round16(h->d * (h->refine == 1 ? 4 : 2)),
+                         (size_t)slab_mb << 20);
+    h->refine_arena.zero_new = true;
+  } else if (json_float(js, "k_factor", 1.0) < 1.0) {
+    delete h;
+    throw std::runtime_error("k_factor must be >= 1");
+  }
   return h;
 }
 
@@ -949,6 +1002,44 @@ static void encode_chunk(dfann_index *h, int64_t n, const float *x,
 static void hnsw_add(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream);
 
+// append n raw rows to the refine store at rows [ntotal, ntotal+n), in
+// arrival order on the caller's stream (the caller bumps ntotal after)
+static void refine_append(dfann_index *h, int64_t n, const float *x,
+                          hipStream_t stream) {
+  SlabArena &ra = h->refine_arena;
+  const int64_t row0 = h->ntotal;
+  ra.ensure_rows(row0 + n);
+  // refreshed here (it synchronizes when a slab was added) so that no
+  // search ever has to
+  uint8_t *const *tab = ra.dev_table_mut(stream);
+  if (h->refine == 2) {
+    hipLaunchKernelGGL(k_refine_store_f16, grid1d(n * h->d), dim3(256), 0,
+                       stream, x, (long long)n, h->d, ra.stride, ra.rlog,
+                       (long long)row0, tab);
+  } else if (ra.stride == 4 * h->d) {
+    // fp32 rows with no pad: device-to-device copies, one per slab touched
+    int64_t r = row0, left = n;
+    const float *src = x;
+    while (left > 0) {
+      int64_t in_slab = std::min<int64_t>(left, ra.rps() - (r & (ra.rps() - 1)));
+      char *dst = (char *)ra.slabs[r >> ra.rlog] +
+                  (size_t)(r & (ra.rps() - 1)) * ra.stride;
+      HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)in_slab * ra.stride,
+                               hipMemcpyDeviceToDevice, stream));
+      src += in_slab * h->d;
+      r += in_slab;
+      left -= in_slab;
+    }
+  } else {
+    // d % 4 != 0: rows are padded to 16 B, so the copy is strided
+    hipLaunchKernelGGL(k_pack_rows, grid1d(n * h->d), dim3(256), 0, stream, x,
+                       (long long)n, h->d, ra.stride, ra.rlog, (long long)row0,
+                       tab);
+  }
+  HIP_CHECK(hipGetLastError());
+  ra.rows = row0 + n;
+}
+
 static void add_impl(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream) {
   if (!h->trained) throw std::runtime_error("add on untrained index");
@@ -976,6 +1067,7 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
     assign_rows(h, x + s * h->d, c, asg.as<int>(), stream);
     int64_t row0 = (int64_t)h->h_pend_assign.size();
     encode_chunk(h, c, x + s * h->d, asg.as<int>(), row0, stream);
+    if (h->refine) refine_append(h, c, x + s * h->d, stream);
     size_t old = h->h_pend_assign.size();
     h->h_pend_assign.resize(old + c);
     HIP_CHECK(hipMemcpyAsync(h->h_pend_assign.data() + old, asg.p,
@@ -1759,6 +1851,47 @@ static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
 }
 
 // ---------------------------------------------------------------------------
+// refine stage
+// ---------------------------------------------------------------------------
+
+// k' = min(512, max(k, ceil(k * k_factor))). A product within 1e-4 above
+// an integer counts as that integer, so a k_factor that went through
+// float32 (1.6f = 1.60000002) still gives k' = 16 at k = 10.
+static int refine_kprime(const dfann_index *h, int k) {
+  int kp = (int)std::ceil((double)k * h->k_factor - 1e-4);
+  kp = std::max(kp, k);
+  return std::min(kp, REFINE_KMAX);
+}
+
+// Runs `base(k', D', I')` (any of the search entries) into the workspace
+// and re-ranks its candidates exactly into the caller's (nq, k) D / I.
+// Stream-ordered, no host sync; the workspace grows only when a shape is
+// first seen, so a warmed-up call captures into a HIP graph.
+template <typename Base>
+static void search_with_refine(dfann_index *h, int64_t nq, const float *q,
+                               int k, float *D, int64_t *I, hipStream_t stream,
+                               Base base) {
+  if (!h->refine) { base(k, D, I); return; }
+  if (k > 512) throw std::runtime_error("k > 512 unsupported");
+  if (k < 1) throw std::runtime_error("k < 1");
+  if (nq == 0) return;
+  const int kp = refine_kprime(h, k);
+  h->rf_D.ensure((size_t)nq * kp * 4);
+  h->rf_I.ensure((size_t)nq * kp * 8);
+  base(kp, h->rf_D.as<float>(), h->rf_I.as<int64_t>());
+  SlabArena &ra = h->refine_arena;
+  const uint8_t *const *tab = ra.dev_table(stream);
+  const size_t lds = REFINE_LDS_BYTES(h->d);
+  const bool ip = h->metric == M_IP;
+  auto kern = h->refine == 2 ? (ip ? k_refine<__half, 0> : k_refine<__half, 1>)
+                             : (ip ? k_refine<float, 0> : k_refine<float, 1>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, stream, q, tab,
+                     ra.rlog, ra.stride, (long long)ra.rows,
+                     h->rf_I.as<int64_t>(), (long long)nq, kp, k, h->d, D, I);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
 // C-ABI
 // ---------------------------------------------------------------------------
 
@@ -1798,7 +1931,11 @@ extern "C" int dfann_search(dfann_index *h, int64_t nq, const float *q_dev,
                             int k, float *D_dev, int64_t *I_dev,
                             dfann_stream stream) {
   API_BEGIN
-  search_impl(h, nq, q_dev, k, D_dev, I_dev, (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
+                     [&](int kb, float *Db, int64_t *Ib) {
+                       search_impl(h, nq, q_dev, kb, Db, Ib, s);
+                     });
   API_END
 }
 
@@ -1822,13 +1959,17 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   API_BEGIN
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
-  if (h->ntotal == 0) {
-    pad_fill(h, nq, k, D_dev, I_dev, (hipStream_t)stream);
-    return 0;
-  }
-  finalize_csr(h, (hipStream_t)stream);
-  scan_and_merge(h, nq, q_dev, nprobe, probes_dev, keys_dev, k, D_dev, I_dev,
-                 (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
+                     [&](int kb, float *Db, int64_t *Ib) {
+                       if (h->ntotal == 0) {
+                         pad_fill(h, nq, kb, Db, Ib, s);
+                         return;
+                       }
+                       finalize_csr(h, s);
+                       scan_and_merge(h, nq, q_dev, nprobe, probes_dev,
+                                      keys_dev, kb, Db, Ib, s);
+                     });
   API_END
 }
 
@@ -1839,8 +1980,13 @@ extern "C" int dfann_search_filtered(dfann_index *h, int64_t nq,
                                      int64_t *I_dev, dfann_stream stream) {
   API_BEGIN
   check_filter(h, allow_bits_dev, nbits);
-  search_impl(h, nq, q_dev, k, D_dev, I_dev, (hipStream_t)stream,
-              allow_bits_dev);
+  hipStream_t s = (hipStream_t)stream;
+  // the filter applies in the base stage only: refine sees allowed ids
+  search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
+                     [&](int kb, float *Db, int64_t *Ib) {
+                       search_impl(h, nq, q_dev, kb, Db, Ib, s,
+                                   allow_bits_dev);
+                     });
   API_END
 }
 
@@ -1855,13 +2001,17 @@ extern "C" int dfann_search_preassigned_filtered(
   check_filter(h, allow_bits_dev, nbits);
   if (k > 512) throw std::runtime_error("k > 512 unsupported");
   if (nq == 0) return 0;
-  if (h->ntotal == 0) {
-    pad_fill(h, nq, k, D_dev, I_dev, (hipStream_t)stream);
-    return 0;
-  }
-  finalize_csr(h, (hipStream_t)stream);
-  scan_and_merge(h, nq, q_dev, nprobe, probes_dev, keys_dev, k, D_dev, I_dev,
-                 (hipStream_t)stream, allow_bits_dev);
+  hipStream_t s = (hipStream_t)stream;
+  search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
+                     [&](int kb, float *Db, int64_t *Ib) {
+                       if (h->ntotal == 0) {
+                         pad_fill(h, nq, kb, Db, Ib, s);
+                         return;
+                       }
+                       finalize_csr(h, s);
+                       scan_and_merge(h, nq, q_dev, nprobe, probes_dev,
+                                      keys_dev, kb, Db, Ib, s, allow_bits_dev);
+                     });
   API_END
 }
 
@@ -1870,6 +2020,23 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
                                         float *D_dev, int64_t *I_dev,
                                         float *R_dev, dfann_stream stream) {
   API_BEGIN
+  if (h->refine) {
+    // a refine index returns the STORED rows, not the code decode
+    hipStream_t s = (hipStream_t)stream;
+    search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
+                       [&](int kb, float *Db, int64_t *Ib) {
+                         search_impl(h, nq, q_dev, kb, Db, Ib, s);
+                       });
+    if (nq == 0) return 0;
+    SlabArena &ra = h->refine_arena;
+    auto rk = h->refine == 2 ? k_refine_reconstruct<__half>
+                             : k_refine_reconstruct<float>;
+    hipLaunchKernelGGL(rk, dim3((unsigned)(nq * k)), dim3(64), 0, s, I_dev,
+                       (long long)(nq * k), h->d, ra.dev_table(s), ra.rlog,
+                       ra.stride, (long long)ra.rows, R_dev);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   search_impl(h, nq, q_dev, k, D_dev, I_dev, (hipStream_t)stream);
   int rtype;
   const float *flat_src = nullptr;
@@ -1893,6 +2060,34 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
 extern "C" int dfann_set_nprobe(dfann_index *h, int nprobe) {
   API_BEGIN
   h->nprobe = nprobe;
+  API_END
+}
+
+extern "C" int dfann_set_k_factor(dfann_index *h, float k_factor) {
+  API_BEGIN
+  if (!h->refine)
+    throw std::runtime_error("set_k_factor: index has no refine stage");
+  if (!(k_factor >= 1.0f)) throw std::runtime_error("k_factor must be >= 1");
+  h->k_factor = (double)k_factor;
+  API_END
+}
+
+extern "C" int dfann_refine_info(dfann_index *h, int64_t out[3]) {
+  API_BEGIN
+  out[0] = h->refine;
+  out[1] = h->refine ? h->refine_arena.stride : 0;
+  out[2] = h->refine ? h->refine_arena.rows : 0;
+  API_END
+}
+
+extern "C" int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
+                                     void *out_host) {
+  API_BEGIN
+  if (!h->refine) throw std::runtime_error("index has no refine store");
+  if (row0 < 0 || n < 0 || row0 + n > h->refine_arena.rows)
+    throw std::runtime_error("get_refine_rows: range outside the store");
+  HIP_CHECK(hipDeviceSynchronize());
+  if (n) h->refine_arena.copy_rows_to_host(out_host, row0, n);
   API_END
 }
 
@@ -2104,6 +2299,19 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
         fwrite_chk(tmp.data(), (size_t)c * h->stride, f);
       }
     }
+    if (h->refine && h->ntotal) {
+      // refine payload (only when the spec carries "refine", which the
+      // loader reads back from the same file): the store's ntotal rows
+      // in row (= arrival id) order
+      const SlabArena &ra = h->refine_arena;
+      const int64_t CHROWS = std::max<int64_t>(1, ((int64_t)64 << 20) / ra.stride);
+      std::vector<char> tmp((size_t)std::min(CHROWS, h->ntotal) * ra.stride);
+      for (int64_t r = 0; r < h->ntotal; r += CHROWS) {
+        int64_t c = std::min(CHROWS, h->ntotal - r);
+        ra.copy_rows_to_host(tmp.data(), r, c);
+        fwrite_chk(tmp.data(), (size_t)c * ra.stride, f);
+      }
+    }
   } catch (...) {
     fclose(f);
     throw;
@@ -2229,6 +2437,23 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
           i2p[ids[j]] = (unsigned)j;
       HIP_CHECK(hipMemcpy(h->id2pos.p, i2p.data(), (size_t)h->ntotal * 4,
                           hipMemcpyHostToDevice));
+      HIP_CHECK(hipDeviceSynchronize());
+    }
+    if (h->refine && h->ntotal) {
+      SlabArena &ra = h->refine_arena;
+      const int64_t CHROWS = std::max<int64_t>(1, ((int64_t)64 << 20) / ra.stride);
+      std::vector<char> tmp((size_t)std::min(CHROWS, h->ntotal) * ra.stride);
+      for (int64_t r = 0; r < h->ntotal; r += CHROWS) {
+        int64_t c = std::min(CHROWS, h->ntotal - r);
+        if (fread(tmp.data(), 1, (size_t)c * ra.stride, f) !=
+            (size_t)c * ra.stride)
+          throw std::runtime_error(
+              "dfann file truncated inside the refine payload (rows " +
+              std::to_string(r) + ".." + std::to_string(r + c) + " of " +
+              std::to_string(h->ntotal) + ")");
+        ra.copy_rows_from_host(tmp.data(), r, c);
+      }
+      ra.rows = h->ntotal;
       HIP_CHECK(hipDeviceSynchronize());
     }
   } catch (...) {

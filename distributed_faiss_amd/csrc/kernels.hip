@@ -2625,3 +2625,209 @@ extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
     }
   }
 }
+
+// ---------------------------------------------------------------------------
+// refine stage: exact re-ranking of the base stage's k'
+// candidates against the raw store (fp32 or fp16 rows in arrival order,
+// row id == arrival id, stride round16(d * sizeof(T)), zero pad bytes).
+// ---------------------------------------------------------------------------
+
+// raw-store append, fp16 rows: __float2half is round-to-nearest-even, the
+// conversion k_sq_encode uses (fp32 rows are plain copies, no kernel)
+extern "C" __global__ void k_refine_store_f16(const float *__restrict__ x,
+                                              long long n, int d, int stride,
+                                              int rlog, long long row0,
+                                              uint8_t *const *__restrict__ store) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = n * d;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    long long r = i / d;
+    int t = (int)(i % d);
+    uint8_t *row = slab_row_mut(store, rlog, row0 + r, stride);
+    reinterpret_cast<unsigned short *>(row)[t] =
+        __half_as_ushort(__float2half(x[i]));
+  }
+}
+
+#define REFINE_KMAX 512   // k' cap (== the engine's k cap)
+#define REFINE_SORT_BYTES (REFINE_KMAX * 8)
+#define REFINE_UNROLL 8   // 8-element chunks in flight per lane (d <= 1024
+                          // per batch; larger d loops over batches)
+#define REFINE_LDS_BYTES(d) (REFINE_SORT_BYTES + (((d) + 7) & ~7) * 4)
+
+// one 8-element chunk of a stored row: one 16-B load (fp16), two (fp32)
+template <typename T>
+__device__ __forceinline__ void refine_load(const uint8_t *__restrict__ row,
+                                            int t0, int d, uint4 &a, uint4 &b) {
+  if (std::is_same<T, __half>::value) {
+    a = *reinterpret_cast<const uint4 *>(row + (size_t)t0 * 2);
+  } else {
+    a = *reinterpret_cast<const uint4 *>(row + (size_t)t0 * 4);
+    // the second half may lie past the row's stride when d - t0 <= 4
+    if (t0 + 4 < d)
+      b = *reinterpret_cast<const uint4 *>(row + (size_t)t0 * 4 + 16);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void refine_widen(const uint4 &a, const uint4 &b,
+                                             float *xv) {
+  if (std::is_same<T, __half>::value) {
+    const unsigned w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      xv[2 * j] = __half2float(__ushort_as_half((unsigned short)(w[j] & 0xFFFFu)));
+      xv[2 * j + 1] = __half2float(__ushort_as_half((unsigned short)(w[j] >> 16)));
+    }
+  } else {
+    xv[0] = __uint_as_float(a.x); xv[1] = __uint_as_float(a.y);
+    xv[2] = __uint_as_float(a.z); xv[3] = __uint_as_float(a.w);
+    xv[4] = __uint_as_float(b.x); xv[5] = __uint_as_float(b.y);
+    xv[6] = __uint_as_float(b.z); xv[7] = __uint_as_float(b.w);
+  }
+}
+
+// part = part + term over t = t0 .. t0+7 with t < d, ascending, no fma
+template <int METRIC>
+__device__ __forceinline__ float refine_acc(float part, const float *xv,
+                                            const float *__restrict__ qs,
+                                            int t0, int d) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (t0 + j < d) {
+      float qv = qs[t0 + j];
+      float term;
+      if (METRIC == 0) {
+        term = qv * xv[j];
+      } else {
+        float df = qv - xv[j];
+        term = df * df;
+      }
+      part = part + term;
+    }
+  }
+  return part;
+}
+
+// Exact distances of the (nq, kp) base candidates and the top-k of them.
+// One 256-thread block per query; 16 lanes per candidate row, 16 rows per
+// pass. Lane g of a row owns the 8-element chunks at t0 = 8g, 8g+128, ...
+// and sums them in ascending t; the 16 partials meet in an xor butterfly
+// (8, 4, 2, 1). That order IS the numeric contract (tests/refine_ref.py
+// restates it op for op). Selection: (key, ascending id) through a
+// monotone uint encoding of the minimize key (L2 distance / -dot), packed
+// with the id into one u64 and bitonic-sorted in LDS; candidates that are
+// -1 (base pads) never enter. METRIC: 0 = IP, 1 = L2.
+template <typename T, int METRIC>
+__global__ __launch_bounds__(256) void k_refine(
+    const float *__restrict__ q, const uint8_t *const *__restrict__ store,
+    int rlog, int stride, long long nrows, const int64_t *__restrict__ candI,
+    long long nq, int kp, int k, int d, float *__restrict__ D,
+    int64_t *__restrict__ I) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long *srt = reinterpret_cast<unsigned long long *>(smem);
+  float *qs = reinterpret_cast<float *>(smem + REFINE_SORT_BYTES);
+  const long long qi = blockIdx.x;
+  if (qi >= nq) return;
+  const int d8 = (d + 7) & ~7;
+  for (int t = threadIdx.x; t < d8; t += blockDim.x)
+    qs[t] = t < d ? q[qi * d + t] : 0.f;
+  int P = 16;
+  while (P < kp) P <<= 1;  // kp <= REFINE_KMAX
+  for (int i = threadIdx.x; i < P; i += blockDim.x) srt[i] = ~0ULL;
+  __syncthreads();
+  const int g = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+  for (int r0 = 0; r0 < kp; r0 += 16) {
+    const int r = r0 + rsub;
+    const long long id = r < kp ? candI[qi * kp + r] : -1;
+    const bool ok = id >= 0 && id < nrows;
+    float part = 0.f;
+    if (ok) {
+      const uint8_t *row = slab_row(store, rlog, id, stride);
+      for (int c0 = 8 * g; c0 < d; c0 += 128 * REFINE_UNROLL) {
+        uint4 a[REFINE_UNROLL], b[REFINE_UNROLL];
+        // all of the lane's loads for this batch are issued first
+#pragma unroll
+        for (int u = 0; u < REFINE_UNROLL; ++u) {
+          a[u] = make_uint4(0u, 0u, 0u, 0u);
+          b[u] = make_uint4(0u, 0u, 0u, 0u);
+          const int t0 = c0 + 128 * u;
+          if (t0 < d) refine_load<T>(row, t0, d, a[u], b[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < REFINE_UNROLL; ++u) {
+          const int t0 = c0 + 128 * u;
+          if (t0 < d) {
+            float xv[8];
+            refine_widen<T>(a[u], b[u], xv);
+            part = refine_acc<METRIC>(part, xv, qs, t0, d);
+          }
+        }
+      }
+    }
+    // every lane takes part (rows that are skipped carry 0)
+    part = part + __shfl_xor(part, 8, 16);
+    part = part + __shfl_xor(part, 4, 16);
+    part = part + __shfl_xor(part, 2, 16);
+    part = part + __shfl_xor(part, 1, 16);
+    if (ok && g == 0) {
+      const float key = METRIC == 0 ? -part : part;
+      srt[r] = ((unsigned long long)f32_enc(key) << 32) |
+               (unsigned long long)(unsigned)id;
+    }
+  }
+  for (int kk = 2; kk <= P; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < P; i += blockDim.x) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const unsigned long long vi = srt[i], vj = srt[ixj];
+          const bool asc = (i & kk) == 0;
+          if (asc ? vj < vi : vi < vj) {
+            srt[i] = vj;
+            srt[ixj] = vi;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < k; j += blockDim.x) {
+    const unsigned long long v = j < P ? srt[j] : ~0ULL;
+    if (v != ~0ULL) {
+      const float key = f32_dec((unsigned)(v >> 32));
+      D[qi * k + j] = METRIC == 0 ? -key : key;
+      I[qi * k + j] = (long long)(v & 0xFFFFFFFFULL);
+    } else {
+      D[qi * k + j] = METRIC == 0 ? -DFANN_FLT_MAX : DFANN_FLT_MAX;
+      I[qi * k + j] = -1;
+    }
+  }
+}
+
+// search_reconstruct on a refine index: the STORED rows (fp16 widened,
+// fp32 as is), zeros at pads. One 64-thread block per (q, j).
+template <typename T>
+__global__ __launch_bounds__(64) void k_refine_reconstruct(
+    const int64_t *__restrict__ I, long long n_e, int d,
+    const uint8_t *const *__restrict__ store, int rlog, int stride,
+    long long nrows, float *__restrict__ R) {
+  const long long e = blockIdx.x;
+  if (e >= n_e) return;
+  const long long id = I[e];
+  float *out = R + e * d;
+  if (id < 0 || id >= nrows) {
+    for (int t = threadIdx.x; t < d; t += blockDim.x) out[t] = 0.f;
+    return;
+  }
+  const uint8_t *row = slab_row(store, rlog, id, stride);
+  for (int t = threadIdx.x; t < d; t += blockDim.x) {
+    if (std::is_same<T, __half>::value)
+      out[t] = __half2float(
+          __ushort_as_half(reinterpret_cast<const unsigned short *>(row)[t]));
+    else
+      out[t] = reinterpret_cast<const float *>(row)[t];
+  }
+}

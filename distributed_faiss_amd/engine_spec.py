@@ -8,6 +8,8 @@
 #   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq"
 #   dim, metric (0=IP, 1=L2), nlist, m, nbits, sq_type ("fp16"|"8bit"),
 #   nprobe, seed
+#   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
+#   (faiss IndexRefineFlat / IndexRefine)
 #
 # Behavioral quirks kept on purpose (SURVEY.md §2 quirk list):
 #   * builder "flat" ALWAYS builds an inner-product flat index, ignoring
@@ -69,11 +71,11 @@ def _builder_spec(cfg: IndexCfg) -> dict:
             nbits=int(cfg.extra.get("bits_per_vector", 8)),
             nprobe=1,
         )
-        return spec
+        return _apply_refine(cfg, spec)
     if t == "ivfsq":
         # reference index.py:63-68 — QT_fp16
         spec.update(type="ivfsq", nlist=int(cfg.centroids), sq_type="fp16")
-        return spec
+        return _apply_refine(cfg, spec)
     if t == "hnswsq":
         # reference index.py:51-60: faiss.IndexHNSWSQ(dim, QT_8bit,
         # store_n) — L2 asserted; efSearch = cfg.nprobe at build,
@@ -96,7 +98,24 @@ def _builder_spec(cfg: IndexCfg) -> dict:
     raise KeyError(f"unknown index_builder_type {t!r}")
 
 
-_FACTORY_RE = re.compile(r"^IVF(\d+),(Flat|PQ(\d+)|SQ8|SQfp16)$")
+# optional third component, PQ / SQ bases only: faiss IndexRefineFlat
+# ("RFlat") and IndexRefine over an fp16 scalar quantizer ("Refine(SQfp16)")
+_FACTORY_RE = re.compile(
+    r"^IVF(\d+),(?:(Flat)|(PQ(\d+)|SQ8|SQfp16)(?:,(RFlat|Refine\(SQfp16\)))?)$")
+_FACTORY_REFINE = {"RFlat": "fp32", "Refine(SQfp16)": "fp16"}
+
+# Refine keys of cfg.extra. NOT perf knobs: they change results.
+REFINE_KEYS = ("refine", "k_factor")
+
+
+def _apply_refine(cfg: IndexCfg, spec: dict) -> dict:
+    """cfg.extra["refine"] ("fp32"|"fp16", builders knnlm / ivfsq) and
+    cfg.extra["k_factor"] (builders and factory strings)."""
+    if cfg.extra.get("refine"):
+        spec["refine"] = str(cfg.extra["refine"])
+    if "k_factor" in cfg.extra and spec.get("refine"):
+        spec["k_factor"] = float(cfg.extra["k_factor"])
+    return spec
 
 
 def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
@@ -116,18 +135,24 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if not mm:
         raise NotImplementedError(
             f"factory string {s!r} not supported; supported: Flat, IVFn,Flat, "
-            "IVFn,PQm, IVFn,SQ8, IVFn,SQfp16"
+            "IVFn,PQm, IVFn,SQ8, IVFn,SQfp16, and the last three followed "
+            "by ,RFlat or ,Refine(SQfp16)"
         )
     nlist = int(mm.group(1))
-    kind = mm.group(2)
+    kind = mm.group(2) or mm.group(3)
     if kind == "Flat":
         spec.update(type="ivf_flat", nlist=nlist)
-    elif kind.startswith("PQ"):
-        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(3)), nbits=8)
+        return spec
+    if kind.startswith("PQ"):
+        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(4)), nbits=8)
     elif kind == "SQ8":
         spec.update(type="ivfsq", nlist=nlist, sq_type="8bit")
     else:
         spec.update(type="ivfsq", nlist=nlist, sq_type="fp16")
+    if mm.group(5):
+        spec["refine"] = _FACTORY_REFINE[mm.group(5)]
+        if "k_factor" in cfg.extra:
+            spec["k_factor"] = float(cfg.extra["k_factor"])
     return spec
 
 

@@ -82,6 +82,10 @@ def load_lib():
         c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
         c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.dfann_set_nprobe.argtypes = [c.c_void_p, c.c_int]
+    lib.dfann_set_k_factor.argtypes = [c.c_void_p, c.c_float]
+    lib.dfann_refine_info.argtypes = [c.c_void_p, c.c_void_p]
+    lib.dfann_get_refine_rows.argtypes = [c.c_void_p, c.c_int64, c.c_int64,
+                                          c.c_void_p]
     lib.dfann_ntotal.argtypes = [c.c_void_p]
     lib.dfann_ntotal.restype = c.c_int64
     lib.dfann_nlist.argtypes = [c.c_void_p]
@@ -160,6 +164,7 @@ class HipEngine:
                 json.dumps(self.spec).encode(), ctypes.byref(h)))
             self.h = h
         self._nprobe = int(self.spec.get("nprobe", 1))
+        self._k_factor = float(self.spec.get("k_factor", 1.0))
 
     def __del__(self):
         if getattr(self, "h", None) is not None and self.lib is not None:
@@ -188,6 +193,16 @@ class HipEngine:
     def nprobe(self, v):
         self._nprobe = int(v)
         _check(self.lib, self.lib.dfann_set_nprobe(self.h, int(v)))
+
+    @property
+    def k_factor(self):
+        return self._k_factor
+
+    @k_factor.setter
+    def k_factor(self, v):
+        # the engine raises on an index without a refine stage
+        _check(self.lib, self.lib.dfann_set_k_factor(self.h, float(v)))
+        self._k_factor = float(v)
 
     @property
     def d(self):
@@ -400,6 +415,27 @@ class HipEngine:
             cb.ctypes.data_as(ctypes.c_void_p) if cb is not None else None,
             vm.ctypes.data_as(ctypes.c_void_p) if vm is not None else None,
             vd.ctypes.data_as(ctypes.c_void_p) if vd is not None else None))
+
+    # -- refine store introspection (test plumbing) ------------------------
+
+    def refine_info(self):
+        """(kind, stride, rows): kind 0 none / 1 fp32 / 2 fp16, stride the
+        padded row size in bytes, rows the vectors stored."""
+        out = np.empty(3, dtype=np.int64)
+        _check(self.lib, self.lib.dfann_refine_info(
+            self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return tuple(int(v) for v in out)
+
+    def get_refine_rows(self, row0=0, n=None):
+        """Rows [row0, row0+n) of the raw store as stored: (n, stride)
+        uint8, pad bytes included."""
+        _kind, stride, rows = self.refine_info()
+        if n is None:
+            n = rows - row0
+        out = np.empty((max(n, 1), max(stride, 1)), dtype=np.uint8)
+        _check(self.lib, self.lib.dfann_get_refine_rows(
+            self.h, int(row0), int(n), out.ctypes.data_as(ctypes.c_void_p)))
+        return out[:n]
 
     # -- hnsw introspection (test plumbing) -------------------------------
 

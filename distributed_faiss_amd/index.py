@@ -385,6 +385,16 @@ class Index:
             if self.engine is not None:
                 self.engine.nprobe = nprobe
 
+    def set_k_factor(self, k_factor: float):
+        """Refine stage: re-rank ceil(top_k * k_factor) base candidates
+        (faiss IndexRefine.k_factor). The engine raises RuntimeError when
+        the index has no refine stage."""
+        with self.index_lock:
+            if self.engine is None:
+                raise RuntimeError("set_k_factor: index is not built yet")
+            self.engine.k_factor = k_factor
+        self.cfg.extra["k_factor"] = float(k_factor)
+
     def get_state(self):
         with self.index_lock:
             return self.state

@@ -215,6 +215,9 @@ class IndexServer:
     def set_nprobe(self, index_id: str, nprobe: int):
         return self._get_index(index_id).set_nprobe(nprobe)
 
+    def set_k_factor(self, index_id: str, k_factor: float):
+        return self._get_index(index_id).set_k_factor(k_factor)
+
     def get_ids(self, index_id: str = "default") -> set:
         with self.indexes_lock:
             index = self.indexes[index_id]

@@ -32,6 +32,13 @@
  *    scan/merge kernels (CSR positions and merge slots are u32), so one
  *    shard holds at most 4.29e9 vectors. The C-ABI keeps i64 ids; the
  *    1B-vector headline config is 8 shards x 125M, well inside the cap.
+ *  - refine stage: the base stage is searched at
+ *    k' = min(512, max(k, ceil(k * k_factor))). The clamp at 512 is SILENT:
+ *    k = 40 with k_factor = 13 re-ranks 512 candidates, not 520. A product
+ *    k * k_factor within 1e-4 above an integer counts as that integer
+ *    (k_factor travels as float32: 10 * 1.6f re-ranks 16, not 17).
+ *  - refine needs dim <= 15360 (the query is staged in LDS next to the
+ *    512-entry sort buffer).
  */
 #ifndef DFANN_H
 #define DFANN_H
@@ -50,6 +57,13 @@ typedef void *dfann_stream;             /* hipStream_t */
 /* Build an index from a JSON spec {"type": "flat"|"ivf_flat"|"ivfpq"|
  * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int, "nbits": 8,
  * "sq_type": "fp16"|"8bit", "nprobe": int, "seed": int}.
+ * Refine stage, "ivfpq" / "ivfsq" only (faiss IndexRefineFlat /
+ * IndexRefine(SQfp16)): "refine": "fp32"|"fp16" (absent or
+ * "" = off) keeps every added vector raw (round16(dim * 4 or 2) bytes per
+ * row) and re-ranks the base stage's k' candidates exactly; "k_factor":
+ * float >= 1 (default 1.0, see Limits for k'); "refine_slab_mb": slab size
+ * of the raw store (default 64). "refine" on flat / ivf_flat / hnswsq and
+ * k_factor < 1 are errors.
  * Replaces: faiss.IndexFlatIP/IndexFlatL2 (ref index.py:28-30,94),
  * faiss.IndexIVFFlat (ref index.py:38), faiss.IndexIVFPQ (ref
  * index.py:46), faiss.IndexIVFScalarQuantizer + QT_fp16/QT_8bit (ref
@@ -77,7 +91,9 @@ int dfann_search(dfann_index *h, int64_t nq, const float *q_dev, int k,
                  float *D_dev, int64_t *I_dev, dfann_stream stream);
 
 /* Replaces faiss `Index.search_and_reconstruct` at ref index.py:255.
- * R_dev: (nq,k,d) f32 (decoded vectors; zeros at padded slots). */
+ * R_dev: (nq,k,d) f32 (decoded vectors; zeros at padded slots). On a
+ * refine index the rows come from the raw store instead of the code
+ * decode: fp32 rows exactly, fp16 rows widened. */
 int dfann_search_reconstruct(dfann_index *h, int64_t nq, const float *q_dev,
                              int k, float *D_dev, int64_t *I_dev,
                              float *R_dev, dfann_stream stream);
@@ -118,6 +134,20 @@ int dfann_search_preassigned_filtered(dfann_index *h, int64_t nq,
 /* ref index.py:352-356. Effective nprobe is min(nprobe, nlist, 512) at
  * search time (see Limits above); values above 512 warn once. */
 int dfann_set_nprobe(dfann_index *h, int nprobe);
+/* Mirrors faiss IndexRefine::k_factor (the field index_factory's
+ * "...,RFlat" users set through ParameterSpace "k_factor_rf"): changes k'
+ * of every later search, no rebuild. Errors: index without a refine
+ * stage; k_factor < 1. Not persisted by dfann_save (the spec's value is). */
+int dfann_set_k_factor(dfann_index *h, float k_factor);
+/* Mirrors faiss IndexRefine::refine_index (its codec, code_size and
+ * ntotal): out = {kind 0 none / 1 fp32 / 2 fp16, row stride in bytes,
+ * rows stored}. */
+int dfann_refine_info(dfann_index *h, int64_t out[3]);
+/* Mirrors faiss IndexRefine::refine_index->reconstruct_n(row0, n) without
+ * the decode: rows [row0, row0+n) of the raw store to host, stride-padded
+ * (pad bytes are zero). Test plumbing. */
+int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
+                          void *out_host);
 int64_t dfann_ntotal(dfann_index *h);             /* faiss .ntotal */
 int dfann_nlist(dfann_index *h);                  /* faiss .nlist */
 int dfann_is_trained(dfann_index *h);
