@@ -1361,8 +1361,78 @@ static void pad_fill(dfann_index *h, int64_t nq, int k, float *D, int64_t *I,
   HIP_CHECK(hipGetLastError());
 }
 
+// Fused coarse path: k_gemm_bf16_256_topk keeps the NP (nprobe rounded up
+// to a power of two) best (key, list) pairs per row and 256-column tile,
+// k_coarse_reduce_rk picks the final nprobe. No nq x nlist score matrix:
+// ws1 holds the candidates, nq * n_tile * NP * 8 bytes, and all queries
+// go in one launch. Taken for the shapes that reach k_gemm_bf16_256 with
+// a register-path nprobe; DFANN_COARSE_FUSED=0 (A/B knob) or
+// DFANN_GEMM_P3=1 keep the two-pass path.
+static bool coarse_fused_ok(const dfann_index *h, int64_t nq, int nprobe) {
+  if (const char *e = getenv("DFANN_COARSE_FUSED"))  // experiment override
+    if (atoi(e) == 0) return false;
+  if (const char *e = getenv("DFANN_GEMM_P3"))
+    if (atoi(e) == 1) return false;
+  int K = h->d;
+  return h->coarse_bf16 && h->cent_bf16.p && K % 8 == 0 && h->nlist >= 2048 &&
+         nq >= 256 && K >= 64 && use_regsel(nprobe);
+}
+
+template <int NP>
+static void launch_gemm_topk(dim3 g, hipStream_t stream,
+                             const unsigned short *A, const unsigned short *B,
+                             int M, int N, int K, const float *bn, int mode,
+                             float *cand_d, unsigned *cand_p) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gemm_bf16_256_topk<NP>), g, dim3(512),
+                     0, stream, A, B, M, N, K, K, K, (const float *)nullptr,
+                     bn, mode, cand_d, cand_p);
+}
+
+static void coarse_fused(dfann_index *h, int64_t nq, const float *q,
+                         int nprobe, int32_t *probes, float *keys,
+                         hipStream_t stream) {
+  int nlist = h->nlist, K = h->d;
+  int np = 1;
+  while (np < nprobe) np <<= 1;
+  int n_tile = (nlist + 255) / 256;
+  int ncand = n_tile * np;
+  h->ws1.ensure((size_t)nq * ncand * 8);
+  float *cand_d = h->ws1.as<float>();
+  unsigned *cand_p = reinterpret_cast<unsigned *>(cand_d + (size_t)nq * ncand);
+  h->ws_bf16a.ensure((size_t)nq * K * 2);
+  const unsigned short *A = h->ws_bf16a.as<unsigned short>();
+  const unsigned short *B = h->cent_bf16.as<unsigned short>();
+  const float *bn = h->cnorm.as<float>();
+  int mode = h->metric == M_IP ? 0 : 1;
+  dim3 g((unsigned)n_tile, (unsigned)((nq + 255) / 256));
+  TimingEv e;
+  if (h->timing) e = h->ev_begin(stream);
+  hipLaunchKernelGGL(k_f32_to_bf16, grid1d(nq * K), dim3(256), 0, stream, q,
+                     nq * K, h->ws_bf16a.as<unsigned short>());
+  switch (np) {
+    case 1: launch_gemm_topk<1>(g, stream, A, B, (int)nq, nlist, K, bn, mode, cand_d, cand_p); break;
+    case 2: launch_gemm_topk<2>(g, stream, A, B, (int)nq, nlist, K, bn, mode, cand_d, cand_p); break;
+    case 4: launch_gemm_topk<4>(g, stream, A, B, (int)nq, nlist, K, bn, mode, cand_d, cand_p); break;
+    case 8: launch_gemm_topk<8>(g, stream, A, B, (int)nq, nlist, K, bn, mode, cand_d, cand_p); break;
+    default: launch_gemm_topk<16>(g, stream, A, B, (int)nq, nlist, K, bn, mode, cand_d, cand_p); break;
+  }
+  if (h->timing) {
+    h->ev_end(e, stream, h->ev_gemm);
+    h->gemm_flops += 2LL * nq * nlist * K;
+  }
+  unsigned bs = ncand <= 256 ? 64 : ncand <= 1024 ? 128 : 256;
+  hipLaunchKernelGGL(k_coarse_reduce_rk, dim3((unsigned)nq), dim3(bs),
+                     REGSEL_LDS_BYTES, stream, cand_d, cand_p, (long long)nq,
+                     ncand, nprobe, keys, reinterpret_cast<unsigned *>(probes));
+  HIP_CHECK(hipGetLastError());
+}
+
 static void coarse_impl(dfann_index *h, int64_t nq, const float *q, int nprobe,
                         int32_t *probes, float *keys, hipStream_t stream) {
+  if (coarse_fused_ok(h, nq, nprobe)) {
+    coarse_fused(h, nq, q, nprobe, probes, keys, stream);
+    return;
+  }
   int nlist = h->nlist;
   int64_t chunk = std::max<int64_t>(1, ((int64_t)h->ws_mb << 20) / ((int64_t)nlist * 4));
   chunk = std::min<int64_t>(chunk, nq);

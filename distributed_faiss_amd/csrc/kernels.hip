@@ -879,8 +879,141 @@ extern "C" __global__ __launch_bounds__(512) void k_gemm_bf16_256(
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// k_gemm_bf16_256 with the coarse select fused into the epilogue: same
+// staging, swizzle, MFMA loop and accumulator layout (the GLDS2_* macros
+// above, left defined for it), same gemm_key() on the same accumulators — but C is never
+// stored. Each block reduces its 256x256 key tile to the NP smallest
+// (key, col) pairs per row (sel_less order) and writes them to a
+// candidate buffer laid out (row, n_tile, NP); k_coarse_reduce_rk picks
+// the final nprobe. Slots without a valid column stay (FLT_MAX, PAD_POS);
+// rows >= M write nothing.
+//
+// Epilogue: the 128 KB operand buffer is reused as a 256x128 fp32 tile,
+// filled in two passes (tj 0-1, then tj 2-3, so all 8 waves store in
+// both). Thread t owns row t>>1, 64-column chunk t&1, and streams it
+// through a RegTopK<NP> with ds_read_b128; the start slot is rotated by
+// t so the 16 lanes of a read group (distinct t mod 16) hit 16 distinct
+// 16-B slots of the 256-B bank row. Push order does not matter: (key,
+// col) is a strict total order. The two threads of a row then exchange
+// their lists by shuffle.
+// ---------------------------------------------------------------------------
+template <int NP>
+__global__ __launch_bounds__(512) void k_gemm_bf16_256_topk(
+    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
+    int M, int N, int K, int lda, int ldb, const float *__restrict__ qn,
+    const float *__restrict__ bn, int mode, float *__restrict__ cand_d,
+    unsigned *__restrict__ cand_p) {
+  __shared__ unsigned short smem2[2][2][GB2_T][GB_K];
+  int bi = blockIdx.y * GB2_T;
+  int bj = blockIdx.x * GB2_T;
+  int tid = threadIdx.x;
+  int lane = tid & 63, w = tid >> 6;
+  int wr = (w >> 2) * 128, wc = (w & 3) * 64;
+  f32x4 acc[8][4] = {};
+  int li = lane & 15;
+  int ke = (lane >> 4) * 8;
+
+  GLDS2_STAGE(0, 0)
+  __syncthreads();
+  int cur = 0;
+  for (int k0 = GB_K; k0 < K; k0 += GB_K) {
+    GLDS2_STAGE(cur ^ 1, k0)
+    GLDS2_MFMA(cur)
+    __syncthreads();
+    cur ^= 1;
+  }
+  GLDS2_MFMA(cur)
+  __syncthreads();  // every wave is done with the operand tiles
+
+  float *tile = reinterpret_cast<float *>(&smem2[0][0][0][0]);  // [256][128]
+  int rrow = (lane >> 4) * 4;
+  int srow = tid >> 1, sch = tid & 1;
+  int grow = bi + srow;
+  RegTopK<NP> loc;
+  loc.init();
+#pragma unroll
+  for (int hf = 0; hf < 2; ++hf) {
+    if (hf) __syncthreads();  // first half consumed
+#pragma unroll
+    for (int ti = 0; ti < 8; ++ti) {
+#pragma unroll
+      for (int tjl = 0; tjl < 2; ++tjl) {
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          int lrow = wr + ti * 16 + rrow + rg;
+          int row = bi + lrow;
+          int col = bj + wc + (hf * 2 + tjl) * 16 + li;
+          float key = DFANN_FLT_MAX;
+          if (row < M && col < N)
+            key = gemm_key(acc[ti][hf * 2 + tjl][rg], row, col, qn, bn, mode);
+          tile[lrow * 128 + (w & 3) * 32 + tjl * 16 + li] = key;
+        }
+      }
+    }
+    __syncthreads();
+    const float4 *rp =
+        reinterpret_cast<const float4 *>(tile + srow * 128 + sch * 64);
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {
+      int s = (j + tid) & 15;
+      float4 v = rp[s];
+      // tile column -> global column (4 consecutive share a 16-col group)
+      int lc = sch * 64 + s * 4;
+      int col = bj + (lc >> 5) * 64 + (hf * 2 + ((lc >> 4) & 1)) * 16 +
+                (lc & 15);
+      if (grow < M) {
+        if (col + 0 < N) loc.push(v.x, (unsigned)(col + 0));
+        if (col + 1 < N) loc.push(v.y, (unsigned)(col + 1));
+        if (col + 2 < N) loc.push(v.z, (unsigned)(col + 2));
+        if (col + 3 < N) loc.push(v.w, (unsigned)(col + 3));
+      }
+    }
+  }
+  // merge the row's two 64-column chunks (lanes t, t^1)
+  float od[NP];
+  unsigned op[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    od[i] = __shfl_xor(loc.d[i], 1, 64);
+    op[i] = __shfl_xor(loc.p[i], 1, 64);
+  }
+#pragma unroll
+  for (int i = 0; i < NP; ++i) loc.push(od[i], op[i]);
+  if (sch == 0 && grow < M) {
+    size_t o = ((size_t)grow * gridDim.x + blockIdx.x) * NP;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      cand_d[o + i] = loc.d[i];
+      cand_p[o + i] = loc.p[i];
+    }
+  }
 #undef GLDS2_STAGE
 #undef GLDS2_MFMA
+}
+
+// second stage of the fused coarse select: per query row, the top k of
+// the ncand = n_tile * NP candidates by (key, pos); pads are skipped.
+// Output layout as k_topk_rows_rk with ldo = k. blockDim: 64..256.
+extern "C" __global__ __launch_bounds__(256) void k_coarse_reduce_rk(
+    const float *__restrict__ cand_d, const unsigned *__restrict__ cand_p,
+    long long rows, int ncand, int k, float *__restrict__ out_d,
+    unsigned *__restrict__ out_p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  long long row = blockIdx.x;
+  if (row >= rows) return;
+  RegTopK<16> loc;
+  loc.init();
+  const float *cd = cand_d + row * ncand;
+  const unsigned *cp = cand_p + row * ncand;
+  for (int c = threadIdx.x; c < ncand; c += blockDim.x) {
+    unsigned p = cp[c];
+    if (p != PAD_POS) loc.push(cd[c], p);
+  }
+  __syncthreads();
+  regtopk_block_extract<16>(loc, k, smem, out_d + row * k, out_p + row * k);
 }
 
 // ---------------------------------------------------------------------------
