@@ -388,6 +388,16 @@ struct dfann_index {
 
 static bool use_regsel(int k) { return k <= 16; }
 
+// Wave-per-query merges (k_merge_cand_w / k_merge_shards_w): register-path
+// k and at most 256 candidates per query, i.e. four per lane.
+// DFANN_MERGE_WAVE=0 (A/B knob, read per call) keeps the block-per-query
+// kernels.
+static bool merge_wave_ok(int k, int64_t C) {
+  if (const char *e = getenv("DFANN_MERGE_WAVE"))  // experiment override
+    if (atoi(e) == 0) return false;
+  return use_regsel(k) && C <= 256;
+}
+
 static dim3 grid1d(int64_t total, int block = 256, int64_t cap = 65535LL * 8) {
   int64_t g = (total + block - 1) / block;
   if (g > cap) g = cap;
@@ -1782,7 +1792,12 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   }
   TimingEv em;
   if (h->timing) em = h->ev_begin(stream);
-  if (use_regsel(k)) {
+  if (merge_wave_ok(k, (int64_t)nprobe * fan * k)) {
+    hipLaunchKernelGGL(k_merge_cand_w, dim3((unsigned)((nq + 3) / 4)),
+                       dim3(256), 0, stream, cand_d, cand_p, nq,
+                       nprobe * fan * k, k, h->cr_ids.as<int64_t>(), ip ? 1 : 0,
+                       D, I);
+  } else if (use_regsel(k)) {
     hipLaunchKernelGGL(k_merge_cand_rk, dim3((unsigned)nq), dim3(256),
                        REGSEL_LDS_BYTES + 128, stream, cand_d, cand_p, nq,
                        nprobe * fan * k, k, h->cr_ids.as<int64_t>(), ip ? 1 : 0,
@@ -2272,7 +2287,11 @@ extern "C" int dfann_merge_topk(int64_t nq, int S, int k, const float *D_dev,
   API_BEGIN
   (void)I_dev;  // slots map to metadata host-side (ref client.py:297-298)
   if (k > 512) throw std::runtime_error("k > 512 unsupported");
-  if (use_regsel(k)) {
+  if (merge_wave_ok(k, (int64_t)S * k)) {
+    hipLaunchKernelGGL(k_merge_shards_w, dim3((unsigned)((nq + 3) / 4)),
+                       dim3(256), 0, (hipStream_t)stream, D_dev, nq, S, k,
+                       maximize, Dout_dev, Iout_dev);
+  } else if (use_regsel(k)) {
     hipLaunchKernelGGL(k_merge_shards_rk, dim3((unsigned)nq), dim3(256),
                        REGSEL_LDS_BYTES + 128, (hipStream_t)stream, D_dev, nq,
                        S, k, maximize, Dout_dev, Iout_dev);

@@ -1228,6 +1228,22 @@ extern "C" __global__ __launch_bounds__(256) void k_assign_rowblock(
     }                                                                          \
   }
 
+// m % 16 == 0: no per-code guard can fire, so a group is straight-line
+// code — the 16 lookups are issued back to back and summed afterwards
+// (the guarded form's branches made every lookup wait out its own LDS
+// round trip). Same ascending-order f32 sum -> same bits.
+#define DFANN_PROC16_PQ_FULL(WV, G)                                            \
+  if ((G) < m) {                                                               \
+    unsigned w0_ = (WV).x, w1_ = (WV).y, w2_ = (WV).z, w3_ = (WV).w;           \
+    float v_[16];                                                              \
+    _Pragma("unroll") for (int b = 0; b < 16; ++b) {                           \
+      unsigned word = (b < 4) ? w0_ : (b < 8) ? w1_ : (b < 12) ? w2_ : w3_;    \
+      unsigned c = (word >> ((b & 3) * 8)) & 0xFFu;                            \
+      v_[b] = (float)lut[((G) + b) * 256 + c];                                 \
+    }                                                                          \
+    _Pragma("unroll") for (int b = 0; b < 16; ++b) acc = acc + v_[b];          \
+  }
+
 // SQ8 distance with the decode algebra FOLDED:
 // L2:  diff = u[t] - c*v[t],  u = (q-cent-vmin) - 0.5*scale, v = scale
 // IP:  acc += u[t] + c*v[t],  u = q*vmin + 0.5*(q*scale),   v = q*scale
@@ -1282,6 +1298,20 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
   if (FAM == 0) {
     using LT = typename std::conditional<L16, __half, float>::type;
     const LT *lut = reinterpret_cast<const LT *>(fam);
+    if ((m & 15) == 0) {  // wave-uniform
+      for (int g0 = 0; g0 < m; g0 += 64) {
+#pragma clang fp contract(off)
+        uint4 wa = *reinterpret_cast<const uint4 *>(cp + g0);
+        uint4 wb = (g0 + 16 < m) ? *reinterpret_cast<const uint4 *>(cp + g0 + 16) : zero4;
+        uint4 wc = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(cp + g0 + 32) : zero4;
+        uint4 wd4 = (g0 + 48 < m) ? *reinterpret_cast<const uint4 *>(cp + g0 + 48) : zero4;
+        DFANN_PROC16_PQ_FULL(wa, g0)
+        DFANN_PROC16_PQ_FULL(wb, g0 + 16)
+        DFANN_PROC16_PQ_FULL(wc, g0 + 32)
+        DFANN_PROC16_PQ_FULL(wd4, g0 + 48)
+      }
+      return acc;
+    }
     for (int g0 = 0; g0 < m; g0 += 64) {
 #pragma clang fp contract(off)
       uint4 wa = *reinterpret_cast<const uint4 *>(cp + g0);
@@ -1949,12 +1979,11 @@ INSTANTIATE_SCAN_GHP(k_scan_pq_ip_ghp16, true, 16)
 // variant measured 1.7x slower per byte than 4-B stores (1.3 vs
 // 2.3 TB/s); half the wave covers row rr, the other half rr+1, so LDS
 // and occupancy are unchanged.
-template <typename LUTT, int DSUB, bool PAIRED = false>
+template <typename LUTT, int DSUB, bool PAIRED, bool IS_IP>
 __device__ __forceinline__ void pq_lut_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const int *__restrict__ probes, int nq,
-    int nprobe, int d, int m, int dsub_rt, int is_ip,
-    LUTT *__restrict__ out) {
+    int nprobe, int d, int m, int dsub_rt, LUTT *__restrict__ out) {
   const int dsub = DSUB > 0 ? DSUB : dsub_rt;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int pad = dsub | 1;  // odd stride -> gcd(pad, banks) == 1
@@ -1974,7 +2003,7 @@ __device__ __forceinline__ void pq_lut_body(
     long long qp = qp0 + rr;
     int bq = (int)(qp / nprobe);
     float qv = q[(size_t)bq * d + (size_t)j * dsub + t];
-    if (is_ip) {
+    if (IS_IP) {
       r_sm[rr * pad + t] = qv;
     } else {
       int L = probes[qp];
@@ -2005,7 +2034,7 @@ __device__ __forceinline__ void pq_lut_body(
 #pragma clang fp contract(off)
 #pragma unroll
           for (int cc = 0; cc < 4; ++cc) {
-            if (is_ip) {
+            if (IS_IP) {
               a[cc] = a[cc] + rs[t] * cr[cc][t];
             } else {
               float dd = rs[t] - cr[cc][t];
@@ -2042,7 +2071,7 @@ __device__ __forceinline__ void pq_lut_body(
 #pragma unroll
       for (int t = 0; t < DSUB; ++t) {
 #pragma clang fp contract(off)
-        if (is_ip) {
+        if (IS_IP) {
           acc = acc + rs[t] * creg[t];
         } else {
           float diff = rs[t] - creg[t];
@@ -2058,7 +2087,7 @@ __device__ __forceinline__ void pq_lut_body(
       float acc = 0.f;
       for (int t = 0; t < dsub; ++t) {
 #pragma clang fp contract(off)
-        if (is_ip) {
+        if (IS_IP) {
           acc = acc + rs[t] * crow[t];
         } else {
           float diff = rs[t] - crow[t];
@@ -2071,34 +2100,40 @@ __device__ __forceinline__ void pq_lut_body(
   }
 }
 
-#define DFANN_PQ_LUT_DISPATCH(LUTT, PAIRED, OUT)                               \
+// IS_IP is a compile-time flag: a runtime test inside the unrolled loops
+// gets if-converted, i.e. BOTH metrics computed per entry, then selected.
+#define DFANN_PQ_LUT_CASE(LUTT, DS, PAIRED, IP, OUT)                           \
+  pq_lut_body<LUTT, DS, PAIRED, IP>(q, cent, cb, probes, nq, nprobe, d, m,     \
+                                    dsub, OUT)
+#define DFANN_PQ_LUT_DISPATCH(LUTT, PAIRED, IP, OUT)                           \
   switch (dsub) {                                                              \
-    case 2: pq_lut_body<LUTT, 2, PAIRED>(q, cent, cb, probes, nq, nprobe, d,   \
-                                         m, dsub, is_ip, OUT); break;          \
-    case 4: pq_lut_body<LUTT, 4, PAIRED>(q, cent, cb, probes, nq, nprobe, d,   \
-                                         m, dsub, is_ip, OUT); break;          \
-    case 6: pq_lut_body<LUTT, 6, PAIRED>(q, cent, cb, probes, nq, nprobe, d,   \
-                                         m, dsub, is_ip, OUT); break;          \
-    case 8: pq_lut_body<LUTT, 8, PAIRED>(q, cent, cb, probes, nq, nprobe, d,   \
-                                         m, dsub, is_ip, OUT); break;          \
-    case 12: pq_lut_body<LUTT, 12, PAIRED>(q, cent, cb, probes, nq, nprobe,    \
-                                           d, m, dsub, is_ip, OUT); break;     \
-    case 16: pq_lut_body<LUTT, 16, PAIRED>(q, cent, cb, probes, nq, nprobe,    \
-                                           d, m, dsub, is_ip, OUT); break;     \
-    default: pq_lut_body<LUTT, 0, false>(q, cent, cb, probes, nq, nprobe, d,   \
-                                         m, dsub, is_ip, OUT); break;          \
+    case 2: DFANN_PQ_LUT_CASE(LUTT, 2, PAIRED, IP, OUT); break;                \
+    case 4: DFANN_PQ_LUT_CASE(LUTT, 4, PAIRED, IP, OUT); break;                \
+    case 6: DFANN_PQ_LUT_CASE(LUTT, 6, PAIRED, IP, OUT); break;                \
+    case 8: DFANN_PQ_LUT_CASE(LUTT, 8, PAIRED, IP, OUT); break;                \
+    case 12: DFANN_PQ_LUT_CASE(LUTT, 12, PAIRED, IP, OUT); break;              \
+    case 16: DFANN_PQ_LUT_CASE(LUTT, 16, PAIRED, IP, OUT); break;              \
+    default: DFANN_PQ_LUT_CASE(LUTT, 0, false, IP, OUT); break;                \
   }
 
 extern "C" __global__ __launch_bounds__(256) void k_pq_lut(
     const float *q, const float *cent, const float *cb, const int *probes,
     int nq, int nprobe, int d, int m, int dsub, int is_ip, float *out) {
-  DFANN_PQ_LUT_DISPATCH(float, false, out)
+  if (is_ip) {
+    DFANN_PQ_LUT_DISPATCH(float, false, true, out)
+  } else {
+    DFANN_PQ_LUT_DISPATCH(float, false, false, out)
+  }
 }
 
 extern "C" __global__ __launch_bounds__(256) void k_pq_lut_f16(
     const float *q, const float *cent, const float *cb, const int *probes,
     int nq, int nprobe, int d, int m, int dsub, int is_ip, __half *out) {
-  DFANN_PQ_LUT_DISPATCH(__half, true, out)
+  if (is_ip) {
+    DFANN_PQ_LUT_DISPATCH(__half, true, true, out)
+  } else {
+    DFANN_PQ_LUT_DISPATCH(__half, true, false, out)
+  }
 }
 #define INSTANTIATE_SCAN_NT(NAME, FAM, IS_IP, REGSEL)                          \
   extern "C" __global__ __launch_bounds__(512) void NAME(                      \
@@ -2388,6 +2423,161 @@ extern "C" __global__ __launch_bounds__(256) void k_merge_shards_rk(
     Dout[qi * k + j] = od[j];
     Iout[qi * k + j] = ((long long)sh * nq + qi) * k + jj;
   }
+}
+
+// ---------------------------------------------------------------------------
+// one-wave top-k by rank counting (merges of at most 256 candidates).
+// The wave holds n candidates, candidate i = s*64 + lane in (key[s],
+// pay[s]); whatever lies at i >= n is ignored and ranks as a pad. Every
+// occupied candidate is broadcast once (v_readlane, wave-uniform index)
+// and each lane counts those that precede its own in sel_less order;
+// exact (key, payload) duplicates and pads are ordered by candidate
+// index, so the ranks are a permutation of [0, 64*CPL) and the lane
+// whose candidate has rank r < k owns output slot r. No LDS, no barrier,
+// no dependent shuffle chain. rank[s] >= k: not among the k smallest.
+// ---------------------------------------------------------------------------
+template <int CPL>
+__device__ __forceinline__ void wave_rank_topk(const float (&key)[CPL],
+                                               const unsigned (&pay)[CPL],
+                                               int n, int (&rank)[CPL]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int s = 0; s < CPL; ++s) rank[s] = 0;
+#pragma unroll
+  for (int ss = 0; ss < CPL; ++ss) {
+    int cnt = n - ss * 64;
+    cnt = cnt > 64 ? 64 : cnt;
+    for (int l = 0; l < cnt; ++l) {  // wave-uniform trip count
+      float bk = __int_as_float(
+          __builtin_amdgcn_readlane(__float_as_int(key[ss]), l));
+      unsigned bp = (unsigned)__builtin_amdgcn_readlane((int)pay[ss], l);
+      int bi = ss * 64 + l;
+#pragma unroll
+      for (int s = 0; s < CPL; ++s) {
+        bool before = sel_less(bk, bp, key[s], pay[s]) ||
+                      (bk == key[s] && bp == pay[s] && bi < s * 64 + lane);
+        rank[s] += before ? 1 : 0;
+      }
+    }
+  }
+  // an unoccupied candidate follows all n occupied ones and the
+  // unoccupied ones below it: its rank is its own index
+#pragma unroll
+  for (int s = 0; s < CPL; ++s)
+    if (s * 64 + lane >= n) rank[s] = s * 64 + lane;
+}
+
+// k_merge_cand_rk for C <= 64*CPL on one wave. A candidate the register
+// path never admits (pos == PAD_POS, or a key that is not sel_less than
+// the (FLT_MAX, PAD_POS) sentinel: +inf / NaN) becomes a pad.
+template <int CPL>
+__device__ __forceinline__ void merge_cand_wave(
+    const float *__restrict__ cd, const unsigned *__restrict__ cp, int C,
+    int k, const int64_t *__restrict__ ids, int is_ip, float *__restrict__ D,
+    int64_t *__restrict__ I) {
+  const int lane = threadIdx.x & 63;
+  float key[CPL];
+  unsigned pay[CPL];
+  int rank[CPL];
+#pragma unroll
+  for (int s = 0; s < CPL; ++s) {
+    int c = s * 64 + lane;
+    key[s] = DFANN_FLT_MAX;
+    pay[s] = PAD_POS;
+    if (c < C) {
+      unsigned pos = cp[c];
+      if (pos != PAD_POS) {
+        unsigned idu = ids ? (unsigned)ids[pos] : pos;
+        float kd = cd[c];
+        if (sel_less(kd, idu, DFANN_FLT_MAX, PAD_POS)) {
+          key[s] = kd;
+          pay[s] = idu;
+        }
+      }
+    }
+  }
+  wave_rank_topk<CPL>(key, pay, C, rank);
+#pragma unroll
+  for (int s = 0; s < CPL; ++s) {
+    int r = rank[s];
+    if (r < k) {
+      if (pay[s] != PAD_POS) {
+        D[r] = is_ip ? -key[s] : key[s];
+        I[r] = (long long)pay[s];
+      } else {
+        D[r] = is_ip ? -DFANN_FLT_MAX : DFANN_FLT_MAX;
+        I[r] = -1;
+      }
+    }
+  }
+}
+
+// wave-per-query candidate merge (k <= 16, C <= 256): blockDim/64 queries
+// per block; inputs, id lookup and outputs as k_merge_cand_rk
+extern "C" __global__ __launch_bounds__(256) void k_merge_cand_w(
+    const float *__restrict__ cand_d, const unsigned *__restrict__ cand_p,
+    long long nq, int C, int k, const int64_t *__restrict__ ids, int is_ip,
+    float *__restrict__ D, int64_t *__restrict__ I) {
+  long long qi = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (qi >= nq) return;
+  const float *cd = cand_d + qi * C;
+  const unsigned *cp = cand_p + qi * C;
+  float *Dq = D + qi * k;
+  int64_t *Iq = I + qi * k;
+  if (C <= 64) merge_cand_wave<1>(cd, cp, C, k, ids, is_ip, Dq, Iq);
+  else if (C <= 128) merge_cand_wave<2>(cd, cp, C, k, ids, is_ip, Dq, Iq);
+  else merge_cand_wave<4>(cd, cp, C, k, ids, is_ip, Dq, Iq);
+}
+
+// k_merge_shards_rk for S*k <= 64*CPL on one wave: payload = dense slot
+// s*k + j (the tie-break), maximize negation kept in the output (quirk 2)
+template <int CPL>
+__device__ __forceinline__ void merge_shards_wave(
+    const float *__restrict__ Dall, long long nq, long long qi, int S, int k,
+    int maximize, float *__restrict__ Dout, int64_t *__restrict__ Iout) {
+  const int lane = threadIdx.x & 63;
+  const int C = S * k;
+  float key[CPL];
+  unsigned pay[CPL];
+  int rank[CPL];
+#pragma unroll
+  for (int s = 0; s < CPL; ++s) {
+    int c = s * 64 + lane;
+    key[s] = DFANN_FLT_MAX;
+    pay[s] = PAD_POS;
+    if (c < C) {
+      int sh = c / k, j = c % k;
+      float v = Dall[((long long)sh * nq + qi) * k + j];
+      float kd = maximize ? -v : v;
+      if (sel_less(kd, (unsigned)c, DFANN_FLT_MAX, PAD_POS)) {
+        key[s] = kd;
+        pay[s] = (unsigned)c;
+      }
+    }
+  }
+  wave_rank_topk<CPL>(key, pay, C, rank);
+#pragma unroll
+  for (int s = 0; s < CPL; ++s) {
+    int r = rank[s];
+    if (r < k) {
+      unsigned slot = pay[s];
+      int sh = slot / k, jj = slot % k;
+      Dout[qi * k + r] = key[s];
+      Iout[qi * k + r] = ((long long)sh * nq + qi) * k + jj;
+    }
+  }
+}
+
+// wave-per-query shard merge (k <= 16, S*k <= 256)
+extern "C" __global__ __launch_bounds__(256) void k_merge_shards_w(
+    const float *__restrict__ Dall, long long nq, int S, int k, int maximize,
+    float *__restrict__ Dout, int64_t *__restrict__ Iout) {
+  long long qi = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (qi >= nq) return;
+  int C = S * k;
+  if (C <= 64) merge_shards_wave<1>(Dall, nq, qi, S, k, maximize, Dout, Iout);
+  else if (C <= 128) merge_shards_wave<2>(Dall, nq, qi, S, k, maximize, Dout, Iout);
+  else merge_shards_wave<4>(Dall, nq, qi, S, k, maximize, Dout, Iout);
 }
 
 // ---------------------------------------------------------------------------
