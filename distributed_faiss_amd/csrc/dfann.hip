@@ -388,6 +388,9 @@ struct dfann_index {
 
 static bool use_regsel(int k) { return k <= 16; }
 
+// PQ codewords per sub-quantizer: 256 (nbits=8) or 16 (nbits=4)
+static int pq_ksub(const dfann_index *h) { return 1 << h->nbits; }
+
 // Wave-per-query merges (k_merge_cand_w / k_merge_shards_w): register-path
 // k and at most 256 candidates per query, i.e. four per lane.
 // DFANN_MERGE_WAVE=0 (A/B knob, read per call) keeps the block-per-query
@@ -677,13 +680,31 @@ static dfann_index *create_from_spec(const std::string &js) {
     throw std::runtime_error("bad nlist");
   }
   if (h->type == T_IVFPQ) {
-    if (h->nbits != 8) { delete h; throw std::runtime_error("only nbits=8"); }
+    if (h->nbits != 4 && h->nbits != 8) {
+      int nb = h->nbits;
+      delete h;
+      throw std::runtime_error("ivfpq nbits=" + std::to_string(nb) +
+                               " unsupported (supported: 4, 8)");
+    }
     if (h->m <= 0 || h->d % h->m) {
       delete h;
       throw std::runtime_error("bad m (dim % m != 0)");
     }
     h->dsub = h->d / h->m;
-    h->code_bytes = h->m;
+    h->code_bytes = h->nbits == 4 ? (h->m + 1) / 2 : h->m;
+    if (h->nbits == 4) {
+      // only the in-kernel fp32 LUT exists at 4 bits; a
+      // knob that would change results or layout is refused, not dropped
+      const char *bad = h->pq_lut_f16           ? "pq_lut_f16"
+                        : h->pq_lut_global == 1 ? "pq_lut_global"
+                        : h->pq_pre             ? "pq_precomputed"
+                                                : nullptr;
+      if (bad) {
+        delete h;
+        throw std::runtime_error(std::string("ivfpq nbits=4: ") + bad +
+                                 " unsupported (in-kernel fp32 LUT only)");
+      }
+    }
   } else if (h->type == T_IVFSQ) {
     h->code_bytes = h->sq8 ? h->d : 2 * h->d;
   } else if (h->type == T_IVFFLAT) {
@@ -809,16 +830,17 @@ static void train_impl(dfann_index *h, int64_t n, const float *x,
                        resid.as<float>());
     trace_point("train:residual", stream);
     if (h->type == T_IVFPQ) {
-      h->codebooks.ensure((size_t)h->m * 256 * h->dsub * 4);
+      const int ksub = pq_ksub(h);
+      h->codebooks.ensure((size_t)h->m * ksub * h->dsub * 4);
       DevBuf sub;
       sub.ensure((size_t)n * h->dsub * 4);
       for (int j = 0; j < h->m; ++j) {
         hipLaunchKernelGGL(k_subspace_slice, grid1d(n * h->dsub), dim3(256), 0,
                            stream, resid.as<float>(), n, h->d, j * h->dsub,
                            h->dsub, sub.as<float>());
-        kmeans_device(h, sub.as<float>(), n, 256, h->dsub, M_L2,
+        kmeans_device(h, sub.as<float>(), n, ksub, h->dsub, M_L2,
                       h->seed + 1 + j,
-                      h->codebooks.as<float>() + (size_t)j * 256 * h->dsub,
+                      h->codebooks.as<float>() + (size_t)j * ksub * h->dsub,
                       stream);
         trace_point("train:pq-sub", stream);
       }
@@ -974,30 +996,32 @@ static void encode_chunk(dfann_index *h, int64_t n, const float *x,
     sub.ensure((size_t)n * h->dsub * 4);
     best.ensure((size_t)n * 4);
     bestv.ensure((size_t)n * 4);
-    cbn.ensure(256 * 4);
-    int64_t chunk = std::max<int64_t>(1, ((int64_t)h->ws_mb << 20) / (256 * 4));
+    const int ksub = pq_ksub(h);
+    cbn.ensure(ksub * 4);
+    int64_t chunk = std::max<int64_t>(1, ((int64_t)h->ws_mb << 20) / (ksub * 4));
     chunk = std::min<int64_t>(chunk, n);
-    h->ws1.ensure((size_t)chunk * 256 * 4);
+    h->ws1.ensure((size_t)chunk * ksub * 4);
     for (int j = 0; j < h->m; ++j) {
       hipLaunchKernelGGL(k_subspace_slice, grid1d(n * h->dsub), dim3(256), 0,
                          stream, resid.as<float>(), n, h->d, j * h->dsub,
                          h->dsub, sub.as<float>());
-      const float *cbj = h->codebooks.as<float>() + (size_t)j * 256 * h->dsub;
-      rownorms(cbj, 256, h->dsub, cbn.as<float>(), stream);
+      const float *cbj = h->codebooks.as<float>() + (size_t)j * ksub * h->dsub;
+      rownorms(cbj, ksub, h->dsub, cbn.as<float>(), stream);
       hipLaunchKernelGGL(k_assign_init, grid1d(n), dim3(256), 0, stream,
                          bestv.as<float>(), best.as<int>(), n);
       for (int64_t s0 = 0; s0 < n; s0 += chunk) {
         int64_t c = std::min(chunk, n - s0);
-        gemm_keys(nullptr, sub.as<float>() + s0 * h->dsub, c, cbj, 256,
+        gemm_keys(nullptr, sub.as<float>() + s0 * h->dsub, c, cbj, ksub,
                   h->dsub, cbn.as<float>(), nullptr, 1, h->ws1.as<float>(),
                   stream);
         hipLaunchKernelGGL(k_assign_rowblock, dim3((unsigned)c), dim3(256), 0,
-                           stream, h->ws1.as<float>(), c, (long long)256,
-                           (long long)256, 0, bestv.as<float>() + s0,
+                           stream, h->ws1.as<float>(), c, (long long)ksub,
+                           (long long)ksub, 0, bestv.as<float>() + s0,
                            best.as<int>() + s0);
       }
-      hipLaunchKernelGGL(k_codes_from_best, grid1d(n), dim3(256), 0, stream,
-                         best.as<int>(), n, j, h->stride, rlog, row0, dst);
+      hipLaunchKernelGGL(h->nbits == 4 ? k_codes_from_best4 : k_codes_from_best,
+                         grid1d(n), dim3(256), 0, stream, best.as<int>(), n, j,
+                         h->stride, rlog, row0, dst);
     }
   } else {
     hipLaunchKernelGGL(k_sq_encode, grid1d(n * h->d), dim3(256), 0, stream,
@@ -1515,6 +1539,14 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   bool rk = use_regsel(k);
   switch (h->type) {
     case T_IVFPQ:
+      if (h->nbits == 4) {
+        fam_floats = h->m * 16 + h->d;
+        kern = rk ? (ip ? k_scan_pq4_ip_rk : k_scan_pq4_l2_rk)
+                  : (ip ? k_scan_pq4_ip : k_scan_pq4_l2);
+        kern_f = rk ? (ip ? k_scan_pq4_ip_rk_f : k_scan_pq4_l2_rk_f)
+                    : (ip ? k_scan_pq4_ip_f : k_scan_pq4_l2_f);
+        break;
+      }
       fam_floats = h->m * 256 + h->d;
       kern = rk ? (ip ? k_scan_pq_ip_rk : k_scan_pq_l2_rk)
                 : (ip ? k_scan_pq_ip : k_scan_pq_l2);
@@ -1556,8 +1588,10 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
     default:
       throw std::runtime_error("scan on flat index");
   }
-  bool use_pre = h->type == T_IVFPQ && h->metric == M_L2 && h->pq_pre &&
-                 h->term2.p;
+  // nbits=4 has the in-kernel fp32 LUT only: the PRE / GLUT / fp16 paths
+  // and their env overrides below do not apply to it
+  const bool pq8 = h->type == T_IVFPQ && h->nbits == 8;
+  bool use_pre = pq8 && h->metric == M_L2 && h->pq_pre && h->term2.p;
   if (use_pre) fam_floats = h->m * 256;  // LUT only, no rbuf
   // GLUT path: LUTs built once to HBM by k_pq_lut, scan stages them as
   // coalesced float4 slabs. Auto at m >= 32: the in-kernel build
@@ -1573,7 +1607,7 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   // f32 GLUT measured a wash vs the in-kernel build (BASELINE.md ladder),
   // so auto engages only for the fp16-LUT approximation path where the
   // halved round-trip wins; =1 still forces the f32 variant for A/B.
-  bool use_glut = h->type == T_IVFPQ && !use_pre && h->dsub <= 64 &&
+  bool use_glut = pq8 && !use_pre && h->dsub <= 64 &&
                   (glut_knob == 1 || (glut_knob != 0 && lut_f16));
   lut_f16 = lut_f16 && use_glut;
   if (use_glut)  // LUT only, no rbuf; fam_floats is in FLOAT units
@@ -2127,7 +2161,7 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
   const float *flat_src = nullptr;
   if (h->type == T_FLAT) { rtype = 0; flat_src = h->flat.as<float>(); }
   else if (h->type == T_IVFFLAT) rtype = 0;
-  else if (h->type == T_IVFPQ) rtype = 2;
+  else if (h->type == T_IVFPQ) rtype = h->nbits == 4 ? 6 : 2;
   else if (h->type == T_HNSW) rtype = 5;
   else rtype = h->sq8 ? 3 : 4;
   hipLaunchKernelGGL(k_reconstruct, dim3((unsigned)(nq * k)), dim3(64), 0,
@@ -2201,7 +2235,8 @@ extern "C" int dfann_get_codebooks(dfann_index *h, float *out_host) {
   API_BEGIN
   if (h->type != T_IVFPQ) throw std::runtime_error("not an ivfpq index");
   HIP_CHECK(hipMemcpy(out_host, h->codebooks.p,
-                      (size_t)h->m * 256 * h->dsub * 4, hipMemcpyDeviceToHost));
+                      (size_t)h->m * pq_ksub(h) * h->dsub * 4,
+                      hipMemcpyDeviceToHost));
   API_END
 }
 
@@ -2249,9 +2284,9 @@ extern "C" int dfann_set_trained(dfann_index *h, const float *centroids_host,
   rownorms(h->centroids.as<float>(), h->nlist, h->d, h->cnorm.as<float>(), 0);
   if (h->type == T_IVFPQ) {
     if (!codebooks_host) throw std::runtime_error("codebooks required");
-    h->codebooks.ensure((size_t)h->m * 256 * h->dsub * 4);
+    h->codebooks.ensure((size_t)h->m * pq_ksub(h) * h->dsub * 4);
     HIP_CHECK(hipMemcpy(h->codebooks.p, codebooks_host,
-                        (size_t)h->m * 256 * h->dsub * 4,
+                        (size_t)h->m * pq_ksub(h) * h->dsub * 4,
                         hipMemcpyHostToDevice));
   }
   if (h->type == T_IVFSQ && h->sq8) {
@@ -2348,7 +2383,7 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
       if (h->type != T_HNSW)
         dump_dev(f, h->centroids, (size_t)h->nlist * h->d * 4);
       if (h->type == T_IVFPQ)
-        dump_dev(f, h->codebooks, (size_t)h->m * 256 * h->dsub * 4);
+        dump_dev(f, h->codebooks, (size_t)h->m * pq_ksub(h) * h->dsub * 4);
       if ((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq8) {
         dump_dev(f, h->sq_vmin, (size_t)h->d * 4);
         dump_dev(f, h->sq_vdiff, (size_t)h->d * 4);
@@ -2446,7 +2481,7 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
       h->cnorm.ensure((size_t)h->nlist * 4);
       rownorms(h->centroids.as<float>(), h->nlist, h->d, h->cnorm.as<float>(), 0);
       if (h->type == T_IVFPQ)
-        load_dev(f, h->codebooks, (size_t)h->m * 256 * h->dsub * 4);
+        load_dev(f, h->codebooks, (size_t)h->m * pq_ksub(h) * h->dsub * 4);
       refresh_cent_bf16(h, 0);
       if (h->type == T_IVFSQ && h->sq8) {
         load_dev(f, h->sq_vmin, (size_t)h->d * 4);

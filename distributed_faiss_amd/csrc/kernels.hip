@@ -1244,6 +1244,39 @@ extern "C" __global__ __launch_bounds__(256) void k_assign_rowblock(
     _Pragma("unroll") for (int b = 0; b < 16; ++b) acc = acc + v_[b];          \
   }
 
+// 4-bit PQ (nbits=4): a 16-byte word carries 32 codes,
+// code b in nibble (b & 7) of dword b / 8 (byte b/2, even code low —
+// the faiss ProductQuantizer bit order). LUT rows are 16 floats, so a
+// lane's lookup lands on bank (j*16 + c) % 64: at most 16 distinct
+// addresses on 16 distinct banks per sub-quantizer.
+#define DFANN_PQ4_CODE(W0, W1, W2, W3, B)                                      \
+  (((((B) < 8) ? (W0) : ((B) < 16) ? (W1) : ((B) < 24) ? (W2) : (W3)) >>       \
+    (((B) & 7) * 4)) & 0xFu)
+
+#define DFANN_PROC32_PQ4(WV, G)                                                \
+  if ((G) < m) {                                                               \
+    unsigned w0_ = (WV).x, w1_ = (WV).y, w2_ = (WV).z, w3_ = (WV).w;           \
+    _Pragma("unroll") for (int b = 0; b < 32; ++b) {                           \
+      if ((G) + b < m) {                                                       \
+        unsigned c = DFANN_PQ4_CODE(w0_, w1_, w2_, w3_, b);                    \
+        acc = acc + lut[((G) + b) * 16 + c];                                   \
+      }                                                                        \
+    }                                                                          \
+  }
+
+// m % 32 == 0: straight-line group, as DFANN_PROC16_PQ_FULL — the 32
+// lookups are issued back to back, then summed in ascending order.
+#define DFANN_PROC32_PQ4_FULL(WV, G)                                           \
+  if ((G) < m) {                                                               \
+    unsigned w0_ = (WV).x, w1_ = (WV).y, w2_ = (WV).z, w3_ = (WV).w;           \
+    float v_[32];                                                              \
+    _Pragma("unroll") for (int b = 0; b < 32; ++b) {                           \
+      unsigned c = DFANN_PQ4_CODE(w0_, w1_, w2_, w3_, b);                      \
+      v_[b] = lut[((G) + b) * 16 + c];                                         \
+    }                                                                          \
+    _Pragma("unroll") for (int b = 0; b < 32; ++b) acc = acc + v_[b];          \
+  }
+
 // SQ8 distance with the decode algebra FOLDED:
 // L2:  diff = u[t] - c*v[t],  u = (q-cent-vmin) - 0.5*scale, v = scale
 // IP:  acc += u[t] + c*v[t],  u = q*vmin + 0.5*(q*scale),   v = q*scale
@@ -1289,13 +1322,45 @@ extern "C" __global__ __launch_bounds__(256) void k_assign_rowblock(
     }                                                                          \
   }
 
-template <int FAM, bool IS_IP, bool L16 = false>
+template <int FAM, bool IS_IP, bool L16 = false, bool N4 = false>
 __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
                                                const float *__restrict__ fam,
                                                int d, int m) {
   float acc = 0.f;
   const uint4 zero4 = {0, 0, 0, 0};
-  if (FAM == 0) {
+  if (FAM == 0 && N4) {
+    // 64-byte batches = 128 codes; word w is loaded iff it holds a code
+    // (32w < m), and then lies wholly inside the row: stride is
+    // ceil16((m + 1) / 2) > 16w
+    const float *lut = fam;
+    if ((m & 31) == 0) {  // wave-uniform
+      for (int g0 = 0; g0 < m; g0 += 128) {
+#pragma clang fp contract(off)
+        const uint8_t *rp = cp + (g0 >> 1);
+        uint4 wa = *reinterpret_cast<const uint4 *>(rp);
+        uint4 wb = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(rp + 16) : zero4;
+        uint4 wc = (g0 + 64 < m) ? *reinterpret_cast<const uint4 *>(rp + 32) : zero4;
+        uint4 wd4 = (g0 + 96 < m) ? *reinterpret_cast<const uint4 *>(rp + 48) : zero4;
+        DFANN_PROC32_PQ4_FULL(wa, g0)
+        DFANN_PROC32_PQ4_FULL(wb, g0 + 32)
+        DFANN_PROC32_PQ4_FULL(wc, g0 + 64)
+        DFANN_PROC32_PQ4_FULL(wd4, g0 + 96)
+      }
+      return acc;
+    }
+    for (int g0 = 0; g0 < m; g0 += 128) {
+#pragma clang fp contract(off)
+      const uint8_t *rp = cp + (g0 >> 1);
+      uint4 wa = *reinterpret_cast<const uint4 *>(rp);
+      uint4 wb = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(rp + 16) : zero4;
+      uint4 wc = (g0 + 64 < m) ? *reinterpret_cast<const uint4 *>(rp + 32) : zero4;
+      uint4 wd4 = (g0 + 96 < m) ? *reinterpret_cast<const uint4 *>(rp + 48) : zero4;
+      DFANN_PROC32_PQ4(wa, g0)
+      DFANN_PROC32_PQ4(wb, g0 + 32)
+      DFANN_PROC32_PQ4(wc, g0 + 64)
+      DFANN_PROC32_PQ4(wd4, g0 + 96)
+    }
+  } else if (FAM == 0) {
     using LT = typename std::conditional<L16, __half, float>::type;
     const LT *lut = reinterpret_cast<const LT *>(fam);
     if ((m & 15) == 0) {  // wave-uniform
@@ -1375,7 +1440,7 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
 
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE = false,
           bool GLUT = false, bool L16 = false, bool NT = false, int UR = 4,
-          bool FILT = false>
+          bool FILT = false, bool N4 = false>
 __device__ void ivf_scan_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
@@ -1467,15 +1532,17 @@ __device__ void ivf_scan_body(
           0);
     }
   } else if (FAM == 0) {
-    // rbuf (d floats) AFTER the LUT
+    // rbuf (d floats) AFTER the LUT. N4: 16 codewords per sub-quantizer
+    // (codebook (m, 16, dsub), LUT m*16 floats), same arithmetic.
+    constexpr int KSH = N4 ? 4 : 8, KSUB = 1 << KSH;
     float *lut = fam;
-    float *rbuf = fam + (size_t)m * 256;
+    float *rbuf = fam + (size_t)m * KSUB;
     for (int t = threadIdx.x; t < d; t += blockDim.x)
       rbuf[t] = IS_IP ? qp[t] : qp[t] - cent[(long long)L * d + t];
     __syncthreads();
-    for (int e = threadIdx.x; e < m * 256; e += blockDim.x) {
-      int j = e >> 8, c = e & 255;
-      const float *cbe = cb + ((size_t)j * 256 + c) * dsub;
+    for (int e = threadIdx.x; e < m * KSUB; e += blockDim.x) {
+      int j = e >> KSH, c = e & (KSUB - 1);
+      const float *cbe = cb + ((size_t)j * KSUB + c) * dsub;
       const float *rs = rbuf + j * dsub;
       float acc = 0.f;
       if ((dsub & 3) == 0 && dsub <= 32) {
@@ -1699,7 +1766,10 @@ __device__ void ivf_scan_body(
     // FAM 0 rows are 16-64 B (4 in flight, cheap); FAM 2/3 rows are a
     // full cache line each (8 uint4 in registers), so 2 in flight keeps
     // VGPRs ~100 (5 waves/SIMD) instead of 161 (3 waves).
-    const int UROWS = (FAM == 0) ? 4 : 2;
+    // 4-bit PQ (N4) also takes 2: its 32-lookup groups on top of 4 rows'
+    // load batches cost 183 VGPRs (2 waves/SIMD); 2 rows are 90 (5 waves)
+    // and measured 1.7-2.6x the scan rate (BASELINE.md "4-bit PQ").
+    const int UROWS = (FAM == 0 && !N4) ? 4 : 2;
     const int BS = blockDim.x;
     for (long long base = s0; base < s1; base += (long long)UROWS * BS) {
 #pragma unroll
@@ -1710,7 +1780,7 @@ __device__ void ivf_scan_body(
           bool allow = true;
           if (FILT) allow = pos_allowed(posbits, pos);
           const uint8_t *cp = slab_row(codes, rlog, pos, stride);
-          float acc = scan_row_dist<FAM, IS_IP, L16>(cp, fam, d, m);
+          float acc = scan_row_dist<FAM, IS_IP, L16, N4>(cp, fam, d, m);
           float dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
           if (allow) loc.push(dist, (unsigned)pos);
         }
@@ -1727,7 +1797,7 @@ __device__ void ivf_scan_body(
           bool allow = true;
           if (FILT) allow = pos_allowed(posbits, pos);
           const uint8_t *cp = slab_row(codes, rlog, pos, stride);
-          float acc = scan_row_dist<FAM, IS_IP, L16>(cp, fam, d, m);
+          float acc = scan_row_dist<FAM, IS_IP, L16, N4>(cp, fam, d, m);
           float dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
           if (allow) sel_try(s, dist, (unsigned)pos);
         }
@@ -2249,6 +2319,49 @@ INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_f, true, false, true)
 INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_gh_rk_f, false, true, true)
 INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_rk_f, true, true, true)
 
+// ---------------------------------------------------------------------------
+// 4-bit PQ scans (nbits=4): FAM 0 with N4 set — in-kernel fp32 LUT only
+// (no PRE / GLUT / fp16 twins). Signatures are those of the base and the
+// filtered base kernels, so the dispatcher's `kern` / `kern_f` slots take
+// them unchanged.
+// ---------------------------------------------------------------------------
+
+#define INSTANTIATE_SCAN_N4(NAME, IS_IP, REGSEL)                               \
+  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
+      const float *q, const float *cent, const float *cb,                      \
+      const float *sq_vmin, const float *sq_scale, const int *probes,          \
+      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
+      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
+      float *cand_d, unsigned *cand_p, int fam_floats, int fan) {              \
+    ivf_scan_body<0, IS_IP, REGSEL, false, false, false, false, 4, false,      \
+                  true>(q, cent, cb, sq_vmin, sq_scale, probes, keys, codes,   \
+                        off, nq, nprobe, d, m, dsub, k, stride, rlog, cand_d,  \
+                        cand_p, fam_floats, nullptr, nullptr, nullptr, fan);   \
+  }
+INSTANTIATE_SCAN_N4(k_scan_pq4_l2, false, false)
+INSTANTIATE_SCAN_N4(k_scan_pq4_ip, true, false)
+INSTANTIATE_SCAN_N4(k_scan_pq4_l2_rk, false, true)
+INSTANTIATE_SCAN_N4(k_scan_pq4_ip_rk, true, true)
+
+#define INSTANTIATE_SCAN_N4_F(NAME, IS_IP, REGSEL)                             \
+  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
+      const float *q, const float *cent, const float *cb,                      \
+      const float *sq_vmin, const float *sq_scale, const int *probes,          \
+      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
+      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
+      float *cand_d, unsigned *cand_p, int fam_floats, int fan,                \
+      const unsigned *posbits) {                                               \
+    ivf_scan_body<0, IS_IP, REGSEL, false, false, false, false, 4, true,       \
+                  true>(q, cent, cb, sq_vmin, sq_scale, probes, keys, codes,   \
+                        off, nq, nprobe, d, m, dsub, k, stride, rlog, cand_d,  \
+                        cand_p, fam_floats, nullptr, nullptr, nullptr, fan,    \
+                        nullptr, posbits);                                     \
+  }
+INSTANTIATE_SCAN_N4_F(k_scan_pq4_l2_f, false, false)
+INSTANTIATE_SCAN_N4_F(k_scan_pq4_ip_f, true, false)
+INSTANTIATE_SCAN_N4_F(k_scan_pq4_l2_rk_f, false, true)
+INSTANTIATE_SCAN_N4_F(k_scan_pq4_ip_rk_f, true, true)
+
 // id-space allow-bitmap -> CSR-position-space bitmap: one thread per
 // position p, bit = allow[cr_ids[p]], packed with the 64-lane ballot;
 // lane 0 stores the wave's two words. The tail wave masks p >= ntotal to
@@ -2610,6 +2723,22 @@ extern "C" __global__ void k_codes_from_best(const int *__restrict__ best,
     slab_row_mut(codes, rlog, row0 + p, stride)[j] = (uint8_t)best[p];
 }
 
+// 4-bit twin: sub-quantizer j goes to nibble (j & 1) of byte j / 2. The
+// per-subspace launches are stream-ordered, so an even j writes the whole
+// byte (high nibble 0 — what an odd m leaves in its last byte) and the
+// following odd j ORs into it; no two threads of a launch share a byte.
+extern "C" __global__ void k_codes_from_best4(const int *__restrict__ best,
+                                              long long n, int j, int stride,
+                                              int rlog, long long row0,
+                                              uint8_t *const *__restrict__ codes) {
+  long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; p < n; p += (long long)gridDim.x * blockDim.x) {
+    uint8_t *bp = slab_row_mut(codes, rlog, row0 + p, stride) + (j >> 1);
+    uint8_t c = (uint8_t)(best[p] & 15);
+    *bp = (j & 1) ? (uint8_t)(*bp | (c << 4)) : c;
+  }
+}
+
 // SQ encode (8bit / fp16) of residuals
 extern "C" __global__ void k_sq_encode(const float *__restrict__ resid,
                                        const float *__restrict__ vmin,
@@ -2886,7 +3015,7 @@ extern "C" __global__ void k_minmax_decode(const unsigned *mn, const unsigned *m
 // ---------------------------------------------------------------------------
 // reconstruction: decode result ids -> vectors. One block per (q, j).
 // type: 0 flat/ivfflat raw (flat_src != null uses flat arena directly by id,
-// else CSR codes row), 2 pq, 3 sq8, 4 sqfp16
+// else CSR codes row), 2 pq, 3 sq8, 4 sqfp16, 5 hnsw sq8, 6 pq nbits=4
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
@@ -2935,6 +3064,12 @@ extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
       int j = t / dsub, tt = t % dsub;
       unsigned c = cp[j];
       out[t] = cent[(long long)L * d + t] + cb[((size_t)j * 256 + c) * dsub + tt];
+    }
+  } else if (type == 6) {  // 4-bit pq: (m, 16, dsub) codebook, nibble codes
+    for (int t = threadIdx.x; t < d; t += blockDim.x) {
+      int j = t / dsub, tt = t % dsub;
+      unsigned c = (cp[j >> 1] >> ((j & 1) * 4)) & 15u;
+      out[t] = cent[(long long)L * d + t] + cb[((size_t)j * 16 + c) * dsub + tt];
     }
   } else if (type == 3) {  // sq8
     for (int t = threadIdx.x; t < d; t += blockDim.x) {

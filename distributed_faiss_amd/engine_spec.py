@@ -6,8 +6,8 @@
 # both the HIP engine (distributed_faiss_amd/hip_engine.py) and the test
 # oracle. Engine spec keys:
 #   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq"
-#   dim, metric (0=IP, 1=L2), nlist, m, nbits, sq_type ("fp16"|"8bit"),
-#   nprobe, seed
+#   dim, metric (0=IP, 1=L2), nlist, m, nbits (ivfpq: 4 | 8; DESIGN.md
+#   §6d), sq_type ("fp16"|"8bit"), nprobe, seed
 #   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
 #   (faiss IndexRefineFlat / IndexRefine)
 #
@@ -101,8 +101,11 @@ def _builder_spec(cfg: IndexCfg) -> dict:
 # optional third component, PQ / SQ bases only: faiss IndexRefineFlat
 # ("RFlat") and IndexRefine over an fp16 scalar quantizer ("Refine(SQfp16)")
 _FACTORY_RE = re.compile(
-    r"^IVF(\d+),(?:(Flat)|(PQ(\d+)|SQ8|SQfp16)(?:,(RFlat|Refine\(SQfp16\)))?)$")
+    r"^IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQfp16)"
+    r"(?:,(RFlat|Refine\(SQfp16\)))?)$")
 _FACTORY_REFINE = {"RFlat": "fp32", "Refine(SQfp16)": "fp16"}
+# "PQ<m>x<b>": bits per sub-quantizer code; "PQ<m>" is faiss's default 8
+PQ_NBITS_SUPPORTED = (4, 8)
 
 # Refine keys of cfg.extra. NOT perf knobs: they change results.
 REFINE_KEYS = ("refine", "k_factor")
@@ -135,8 +138,8 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if not mm:
         raise NotImplementedError(
             f"factory string {s!r} not supported; supported: Flat, IVFn,Flat, "
-            "IVFn,PQm, IVFn,SQ8, IVFn,SQfp16, and the last three followed "
-            "by ,RFlat or ,Refine(SQfp16)"
+            "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQfp16, and "
+            "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16)"
         )
     nlist = int(mm.group(1))
     kind = mm.group(2) or mm.group(3)
@@ -144,13 +147,19 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
         spec.update(type="ivf_flat", nlist=nlist)
         return spec
     if kind.startswith("PQ"):
-        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(4)), nbits=8)
+        nbits = int(mm.group(5)) if mm.group(5) else 8
+        if nbits not in PQ_NBITS_SUPPORTED:
+            raise NotImplementedError(
+                f"factory string {s!r}: PQ with {nbits} bits per code not "
+                f"supported; supported: {list(PQ_NBITS_SUPPORTED)}"
+            )
+        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(4)), nbits=nbits)
     elif kind == "SQ8":
         spec.update(type="ivfsq", nlist=nlist, sq_type="8bit")
     else:
         spec.update(type="ivfsq", nlist=nlist, sq_type="fp16")
-    if mm.group(5):
-        spec["refine"] = _FACTORY_REFINE[mm.group(5)]
+    if mm.group(6):
+        spec["refine"] = _FACTORY_REFINE[mm.group(6)]
         if "k_factor" in cfg.extra:
             spec["k_factor"] = float(cfg.extra["k_factor"])
     return spec

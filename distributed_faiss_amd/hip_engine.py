@@ -364,10 +364,13 @@ class HipEngine:
             self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def get_codebooks(self):
+    def _pq_shape(self):
+        """(m, ksub, dsub) of the PQ codebooks; ksub = 1 << nbits."""
         m = int(self.spec["m"])
-        dsub = self.d // m
-        out = np.empty((m, 256, dsub), dtype=np.float32)
+        return m, 1 << int(self.spec.get("nbits", 8)), self.d // m
+
+    def get_codebooks(self):
+        out = np.empty(self._pq_shape(), dtype=np.float32)
         _check(self.lib, self.lib.dfann_get_codebooks(
             self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
@@ -407,7 +410,13 @@ class HipEngine:
             if centroids is not None else None
         cb = np.ascontiguousarray(codebooks, dtype=np.float32) \
             if codebooks is not None else None
-        vm = np.ascontiguousarray(vmin, dtype=np.float32) if vmin is not None else None
+        if cb is not None and self.spec.get("type") == "ivfpq":
+            m, ksub, dsub = self._pq_shape()
+            if cb.size != m * ksub * dsub:
+                raise ValueError(
+                    f"codebooks: expected shape {(m, ksub, dsub)} "
+                    f"(ksub = 1 << nbits), got {cb.shape}")
+        vm =np.ascontiguousarray(vmin, dtype=np.float32) if vmin is not None else None
         vd = np.ascontiguousarray(vdiff, dtype=np.float32) if vdiff is not None else None
         _check(self.lib, self.lib.dfann_set_trained(
             self.h,

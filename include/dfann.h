@@ -55,8 +55,17 @@ typedef void *dfann_stream;             /* hipStream_t */
 /* --- lifecycle -------------------------------------------------------- */
 
 /* Build an index from a JSON spec {"type": "flat"|"ivf_flat"|"ivfpq"|
- * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int, "nbits": 8,
- * "sq_type": "fp16"|"8bit", "nprobe": int, "seed": int}.
+ * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int,
+ * "nbits": 4|8, "sq_type": "fp16"|"8bit", "nprobe": int, "seed": int}.
+ * "ivfpq" codes: "nbits" (default 8) bits per sub-quantizer, 1 << nbits
+ * codewords each; any other value is an error. At 8 a row is m bytes; at
+ * 4 it is (m + 1) / 2 bytes, byte b = code[2b] |
+ * code[2b+1] << 4 (faiss ProductQuantizer bit order; odd m leaves the last
+ * high nibble 0). Rows are padded to a multiple of 16 bytes
+ * (dfann_code_stride). Codebooks are (m, 1 << nbits, dim / m) fp32. At 4
+ * bits only the fp32 LUT built in the scan kernel exists: "pq_lut_f16",
+ * "pq_lut_global": 1 and "pq_precomputed" are errors naming the knob
+ * ("pq_lut_global": -1|0 and "pq_lut_mb" are accepted, without effect).
  * Refine stage, "ivfpq" / "ivfsq" only (faiss IndexRefineFlat /
  * IndexRefine(SQfp16)): "refine": "fp32"|"fp16" (absent or
  * "" = off) keeps every added vector raw (round16(dim * 4 or 2) bytes per
@@ -170,10 +179,13 @@ int dfann_load(const char *path, dfann_index **out);
 int dfann_set_trained(dfann_index *h, const float *centroids_host,
                       const float *codebooks_host, const float *vmin_host,
                       const float *vdiff_host);
-int dfann_get_codebooks(dfann_index *h, float *out_host); /* (m,256,dsub) */
+/* codebooks: (m, 1 << nbits, dsub) fp32 — (m,256,dsub) at nbits=8,
+ * (m,16,dsub) at nbits=4 — for dfann_set_trained and dfann_get_codebooks */
+int dfann_get_codebooks(dfann_index *h, float *out_host);
 /* Dump the finalized inverted lists to host: off (nlist+1 i64), ids
  * (ntotal i64, arrival ids in CSR order), codes (ntotal * stride u8).
- * stride = code_bytes rounded up to 16. Used by the CPU-baseline leg of
+ * stride = code_bytes rounded up to 16 (ivfpq nbits=4: nibble-packed rows,
+ * see dfann_create). Used by the CPU-baseline leg of
  * bench.py to scan the SAME index content the GPU holds. */
 int dfann_get_lists(dfann_index *h, int64_t *off_host, int64_t *ids_host,
                     uint8_t *codes_host);
