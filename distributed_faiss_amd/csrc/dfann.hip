@@ -302,11 +302,14 @@ struct dfann_index {
   int ws_mb = 512;  // chunk budget for key matrices (spec "ws_mb"; tests
                     // shrink it to force the multi-chunk paths)
   int max_ppc = 256;  // k-means subsample cap per centroid (spec "max_ppc")
-  bool coarse_bf16 = false;
+  bool coarse_bf16 = false;  // spec "coarse_bf16": assign/coarse GEMMs on
+                             // bf16 MFMA (~16x f32 rate) — approximate
+                             // ranking path for huge nlist (DESIGN.md §7)
   bool pq_pre = false;  // spec "pq_precomputed": PQ-L2 term2/term3 tables
   int pq_lut_global = -1;  // spec "pq_lut_global": ADC LUTs built to HBM
                            // by k_pq_lut, scan stages them coalesced
-                           // (-1 auto: on at m >= 32; 0 off; 1 force)
+                           // (-1 auto: on together with pq_lut_f16;
+                           // 0 off; 1 force, f32 rows unless pq_lut_f16)
   int pq_lut_mb = 2048;  // spec "pq_lut_mb": LUT chunk budget (measured:
                          // bigger chunks win — launch concurrency beats
                          // LLC residency; sweep in BASELINE.md ladder)
@@ -317,9 +320,8 @@ struct dfann_index {
                             // equivalent): documented tolerance path,
                             // off by default; the exact path stays the
                             // parity contract.
-  int scan_fan = 1;     // spec "scan_fan": list-segment fan (experiment)  // spec "coarse_bf16": assign/coarse GEMMs on
-                             // bf16 MFMA (~16x f32 rate) — approximate
-                             // ranking path for huge nlist (DESIGN.md §7)
+  int scan_fan = 1;  // spec "scan_fan": list-segment fan, clamped to
+                     // 1..16 (experiment; non-PQ scans only)
 
   DevBuf centroids, cnorm, codebooks, sq_vmin, sq_vdiff, sq_scale;
   // CSR code image (slab arena; csr_rows rows grouped by list) + pending
@@ -424,16 +426,9 @@ static void gemm_keys_b(dfann_index *h, const float *A, int64_t Mrows,
     hipLaunchKernelGGL(k_f32_to_bf16, grid1d(Mrows * K), dim3(256), 0, stream,
                        A, Mrows * K, h->ws_bf16a.as<unsigned short>());
     if (K % 8 == 0 && N >= 2048 && Mrows >= 256 && K >= 64) {
-      // big coarse/assign shapes: 256^2-tile glds kernel (512 threads).
-      // DFANN_GEMM_P3=1 selects the BK=32 3-buffer counted-vmcnt ring
-      // (k_gemm_bf16_256_p3) where K % 32 == 0 — experiment knob until
-      // measured on hardware.
+      // big coarse/assign shapes: 256^2-tile glds kernel (512 threads)
       dim3 g2((unsigned)((N + 255) / 256), (unsigned)((Mrows + 255) / 256));
-      bool p3 = false;
-      if (const char *e = getenv("DFANN_GEMM_P3"))
-        p3 = atoi(e) == 1 && (K % 32) == 0;
-      hipLaunchKernelGGL(p3 ? k_gemm_bf16_256_p3 : k_gemm_bf16_256, g2,
-                         dim3(512), 0, stream,
+      hipLaunchKernelGGL(k_gemm_bf16_256, g2, dim3(512), 0, stream,
                          h->ws_bf16a.as<unsigned short>(), B_bf16, keys,
                          (int)Mrows, (int)N, K, K, K, (int)N, qn, bn, mode);
     } else {
@@ -1385,6 +1380,50 @@ static void hnsw_search(dfann_index *h, int64_t nq, const float *q, int k,
 // search
 // ---------------------------------------------------------------------------
 
+// Top-k of each row of a (rows x cols) key matrix into out_d / out_p (row
+// stride ldo, positions offset by `base`): register path for k <= 16
+// (bs_rk threads), LDS-buffer selection otherwise (256, Sel capacity is
+// sized for it). allow != nullptr: the filtered twins.
+static void launch_topk_rows(hipStream_t stream, unsigned bs_rk,
+                             const float *keys, int64_t rows, int64_t cols,
+                             int k, unsigned base, int64_t ldo, float *out_d,
+                             unsigned *out_p, const uint32_t *allow) {
+  bool rk = use_regsel(k);
+  dim3 g((unsigned)rows), b(rk ? bs_rk : 256u);
+  size_t lds = rk ? REGSEL_LDS_BYTES : SEL_LDS_BYTES;
+  if (allow)
+    hipLaunchKernelGGL(rk ? k_topk_rows_rk_f : k_topk_rows_f, g, b, lds,
+                       stream, keys, (long long)rows, (long long)cols,
+                       (long long)cols, k, base, (long long)ldo, out_d, out_p,
+                       allow);
+  else
+    hipLaunchKernelGGL(rk ? k_topk_rows_rk : k_topk_rows, g, b, lds, stream,
+                       keys, (long long)rows, (long long)cols, (long long)cols,
+                       k, base, (long long)ldo, out_d, out_p);
+}
+
+// Merge C candidates per query into the final top-k (D, I). ids maps
+// positions to ids (nullptr: positions are the ids). wave_ok lets the
+// wave-per-query kernel take the shapes merge_wave_ok admits.
+static void launch_merge_cand(hipStream_t stream, const float *cand_d,
+                              const unsigned *cand_p, int64_t nq, int C, int k,
+                              const int64_t *ids, bool ip, float *D,
+                              int64_t *I, bool wave_ok) {
+  if (wave_ok && merge_wave_ok(k, C)) {
+    hipLaunchKernelGGL(k_merge_cand_w, dim3((unsigned)((nq + 3) / 4)),
+                       dim3(256), 0, stream, cand_d, cand_p, nq, C, k, ids,
+                       ip ? 1 : 0, D, I);
+  } else if (use_regsel(k)) {
+    hipLaunchKernelGGL(k_merge_cand_rk, dim3((unsigned)nq), dim3(256),
+                       REGSEL_LDS_BYTES + 128, stream, cand_d, cand_p, nq, C,
+                       k, ids, ip ? 1 : 0, D, I);
+  } else {
+    hipLaunchKernelGGL(k_merge_cand, dim3((unsigned)nq), dim3(256),
+                       SEL_LDS_BYTES, stream, cand_d, cand_p, nq, C, k, ids,
+                       ip ? 1 : 0, D, I);
+  }
+}
+
 static void pad_fill(dfann_index *h, int64_t nq, int k, float *D, int64_t *I,
                      hipStream_t stream) {
   // empty index: all pads — run the merge kernel on zero candidates
@@ -1400,13 +1439,11 @@ static void pad_fill(dfann_index *h, int64_t nq, int k, float *D, int64_t *I,
 // k_coarse_reduce_rk picks the final nprobe. No nq x nlist score matrix:
 // ws1 holds the candidates, nq * n_tile * NP * 8 bytes, and all queries
 // go in one launch. Taken for the shapes that reach k_gemm_bf16_256 with
-// a register-path nprobe; DFANN_COARSE_FUSED=0 (A/B knob) or
-// DFANN_GEMM_P3=1 keep the two-pass path.
+// a register-path nprobe; DFANN_COARSE_FUSED=0 (A/B knob) keeps the
+// two-pass path.
 static bool coarse_fused_ok(const dfann_index *h, int64_t nq, int nprobe) {
   if (const char *e = getenv("DFANN_COARSE_FUSED"))  // experiment override
     if (atoi(e) == 0) return false;
-  if (const char *e = getenv("DFANN_GEMM_P3"))
-    if (atoi(e) == 1) return false;
   int K = h->d;
   return h->coarse_bf16 && h->cent_bf16.p && K % 8 == 0 && h->nlist >= 2048 &&
          nq >= 256 && K >= 64 && use_regsel(nprobe);
@@ -1478,112 +1515,88 @@ static void coarse_impl(dfann_index *h, int64_t nq, const float *q, int nprobe,
                 h->cent_bf16.as<unsigned short>(), nlist, h->d,
                 h->cnorm.as<float>(), nullptr, h->metric == M_IP ? 0 : 1, sc,
                 stream);
-    if (use_regsel(nprobe)) {
-      // 256 measured best (128 is -3%: this kernel is one streaming
-      // phase — no phase diversity to recover, unlike the scans)
-      unsigned tk_bs = 256;
-      if (const char *e = getenv("DFANN_TOPK_BS"))  // experiment override
-        if (int v = atoi(e)) tk_bs = (unsigned)((v / 64) * 64);
-      hipLaunchKernelGGL(k_topk_rows_rk, dim3((unsigned)c), dim3(tk_bs),
-                         REGSEL_LDS_BYTES, stream, sc, c, (long long)nlist,
-                         (long long)nlist, nprobe, 0u, (long long)nprobe,
-                         keys + s * nprobe,
-                         reinterpret_cast<unsigned *>(probes) + s * nprobe);
-    } else {
-      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)c), dim3(256),
-                         SEL_LDS_BYTES, stream, sc, c, (long long)nlist,
-                         (long long)nlist, nprobe, 0u, (long long)nprobe,
-                         keys + s * nprobe,
-                         reinterpret_cast<unsigned *>(probes) + s * nprobe);
-    }
+    // 256 measured best (128 is -3%: this kernel is one streaming
+    // phase — no phase diversity to recover, unlike the scans)
+    unsigned tk_bs = 256;
+    if (const char *e = getenv("DFANN_TOPK_BS"))  // experiment override
+      if (int v = atoi(e)) tk_bs = (unsigned)((v / 64) * 64);
+    launch_topk_rows(stream, tk_bs, sc, c, nlist, nprobe, 0u, nprobe,
+                     keys + s * nprobe,
+                     reinterpret_cast<unsigned *>(probes) + s * nprobe,
+                     nullptr);
   }
   HIP_CHECK(hipGetLastError());
 }
 
-// allow != nullptr: filtered search. The caller's id-space bitmap is
-// translated to CSR-position space (k_filter_id2pos, on every call — a
-// cache keyed on the caller's pointer would go stale silently) and the
-// FILT twins of the scans test one bit per row. Needs a finalized CSR.
-static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
-                           int nprobe, const int32_t *probes,
-                           const float *keys, int k, float *D, int64_t *I,
-                           hipStream_t stream,
-                           const uint32_t *allow = nullptr) {
-  const bool filt = allow != nullptr;
-  const unsigned *posbits = nullptr;
-  if (filt) {
-    // outside the scan timing events: not counted in scan_ms
-    int64_t waves = (h->ntotal + 63) / 64;
-    h->filt_ws.ensure((size_t)waves * 8);
-    hipLaunchKernelGGL(k_filter_id2pos, dim3((unsigned)((waves + 3) / 4)),
-                       dim3(256), 0, stream, allow, h->cr_ids.as<int64_t>(),
-                       (long long)h->ntotal, h->filt_ws.as<unsigned>());
-    posbits = h->filt_ws.as<unsigned>();
-  }
-  // candidate arrays (sized after `fan` is chosen below)
-  float *cand_d;
-  unsigned *cand_p;
-  int fam_floats;
-  void (*kern)(const float *, const float *, const float *, const float *,
-               const float *, const int *, const float *,
-               const uint8_t *const *, const int64_t *, int, int, int, int,
-               int, int, int, int, float *, unsigned *, int, int) = nullptr;
-  // filtered twin of `kern` (same arguments + the position bitmap); the
-  // env-gated experiment kernels have none and are ignored when filtering
-  void (*kern_f)(const float *, const float *, const float *, const float *,
-                 const float *, const int *, const float *,
-                 const uint8_t *const *, const int64_t *, int, int, int, int,
-                 int, int, int, int, float *, unsigned *, int, int,
-                 const unsigned *) = nullptr;
-  bool ip = h->metric == M_IP;
+// ---------------------------------------------------------------------------
+// The inverted-list scan: plan_scan picks mode and launch geometry from
+// the index, scan_kernel maps (mode, metric, selector, filtered) to the
+// kernel, scan_and_merge fills one ScanArgs and launches it. The mode
+// list is DFANN_SCAN_MODES (kernels.hip).
+// ---------------------------------------------------------------------------
+
+#define DFANN_SCAN_ENUM(MODE, ...) SCAN_##MODE,
+enum ScanMode { DFANN_SCAN_MODES(DFANN_SCAN_ENUM, DFANN_SCAN_ENUM) };
+#undef DFANN_SCAN_ENUM
+
+typedef void (*scan_kern_t)(ScanArgs);
+struct ScanKernels {
+  const char *mode;
+  scan_kern_t fn[2][2][2];  // [ip][rk][filt]
+};
+#define DFANN_SCAN_FNS(NAME, MET, SUFFIX)                                      \
+  {{k_scan_##NAME##_##MET##SUFFIX, k_scan_##NAME##_##MET##SUFFIX##_f},         \
+   {k_scan_##NAME##_##MET##SUFFIX##_rk, k_scan_##NAME##_##MET##SUFFIX##_rk_f}}
+#define DFANN_SCAN_ROW(MODE, NAME, SUFFIX, ...)                                \
+  {#MODE, {DFANN_SCAN_FNS(NAME, l2, SUFFIX), DFANN_SCAN_FNS(NAME, ip, SUFFIX)}},
+#define DFANN_SCAN_ROW_L2(MODE, NAME, SUFFIX, ...)                             \
+  {#MODE, {DFANN_SCAN_FNS(NAME, l2, SUFFIX), {}}},
+static const ScanKernels SCAN_KERNELS[] = {
+    DFANN_SCAN_MODES(DFANN_SCAN_ROW, DFANN_SCAN_ROW_L2)};
+#undef DFANN_SCAN_ROW_L2
+#undef DFANN_SCAN_ROW
+#undef DFANN_SCAN_FNS
+
+static scan_kern_t scan_kernel(ScanMode mode, bool ip, bool rk, bool filt) {
+  const ScanKernels &row = SCAN_KERNELS[mode];
+  scan_kern_t fn = row.fn[ip][rk][filt];
+  if (!fn)
+    throw std::runtime_error(std::string("no scan kernel for mode ") +
+                             row.mode + (ip ? " ip" : " l2") +
+                             (rk ? " rk" : "") + (filt ? " filtered" : ""));
+  return fn;
+}
+
+struct ScanPlan {
+  ScanMode mode;
+  int fam_floats;    // staged query terms / LUT per block, in FLOAT units
+  size_t lds;        // dynamic LDS per block
+  unsigned scan_bs;  // threads per block
+  int fan;           // list segments per (query, probe)
+  bool lut_f16;      // GLUT rows are __half
+  int64_t glut_qch;  // GLUT: queries per LUT chunk (not clamped to nq)
+};
+
+static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe) {
+  ScanPlan p;
   bool rk = use_regsel(k);
   switch (h->type) {
     case T_IVFPQ:
       if (h->nbits == 4) {
-        fam_floats = h->m * 16 + h->d;
-        kern = rk ? (ip ? k_scan_pq4_ip_rk : k_scan_pq4_l2_rk)
-                  : (ip ? k_scan_pq4_ip : k_scan_pq4_l2);
-        kern_f = rk ? (ip ? k_scan_pq4_ip_rk_f : k_scan_pq4_l2_rk_f)
-                    : (ip ? k_scan_pq4_ip_f : k_scan_pq4_l2_f);
-        break;
+        p.mode = SCAN_PQ4;
+        p.fam_floats = h->m * 16 + h->d;
+      } else {
+        p.mode = SCAN_PQ;
+        p.fam_floats = h->m * 256 + h->d;
       }
-      fam_floats = h->m * 256 + h->d;
-      kern = rk ? (ip ? k_scan_pq_ip_rk : k_scan_pq_l2_rk)
-                : (ip ? k_scan_pq_ip : k_scan_pq_l2);
-      kern_f = rk ? (ip ? k_scan_pq_ip_rk_f : k_scan_pq_l2_rk_f)
-                  : (ip ? k_scan_pq_ip_f : k_scan_pq_l2_f);
       break;
     case T_IVFFLAT:
-      fam_floats = h->d;
-      kern = rk ? (ip ? k_scan_ivfflat_ip_rk : k_scan_ivfflat_l2_rk)
-                : (ip ? k_scan_ivfflat_ip : k_scan_ivfflat_l2);
-      kern_f = rk ? (ip ? k_scan_ivfflat_ip_rk_f : k_scan_ivfflat_l2_rk_f)
-                  : (ip ? k_scan_ivfflat_ip_f : k_scan_ivfflat_l2_f);
+      p.mode = SCAN_IVFFLAT;
+      p.fam_floats = h->d;
       break;
     case T_IVFSQ:
-      if (h->sq8) {
-        fam_floats = 2 * h->d;
-        kern = rk ? (ip ? k_scan_sq8_ip_rk : k_scan_sq8_l2_rk)
-                  : (ip ? k_scan_sq8_ip : k_scan_sq8_l2);
-        kern_f = rk ? (ip ? k_scan_sq8_ip_rk_f : k_scan_sq8_l2_rk_f)
-                    : (ip ? k_scan_sq8_ip_f : k_scan_sq8_l2_f);
-        // DFANN_SCAN_NT=1: non-temporal code-row loads (A/B experiment)
-        if (rk)
-          if (const char *e = getenv("DFANN_SCAN_NT"))
-            if (atoi(e) == 1)
-              kern = ip ? k_scan_sq8_ip_rk_nt : k_scan_sq8_l2_rk_nt;
-        // DFANN_SCAN_U8=1: 8 rows in flight per wave group (A/B)
-        if (rk)
-          if (const char *e = getenv("DFANN_SCAN_U8"))
-            if (atoi(e) == 1)
-              kern = ip ? k_scan_sq8_ip_rk_u8 : k_scan_sq8_l2_rk_u8;
-      } else {
-        fam_floats = h->d;
-        kern = rk ? (ip ? k_scan_sqf_ip_rk : k_scan_sqf_l2_rk)
-                  : (ip ? k_scan_sqf_ip : k_scan_sqf_l2);
-        kern_f = rk ? (ip ? k_scan_sqf_ip_rk_f : k_scan_sqf_l2_rk_f)
-                    : (ip ? k_scan_sqf_ip_f : k_scan_sqf_l2_f);
-      }
+      p.mode = h->sq8 ? SCAN_SQ8 : SCAN_SQF;
+      p.fam_floats = h->sq8 ? 2 * h->d : h->d;
       break;
     default:
       throw std::runtime_error("scan on flat index");
@@ -1592,12 +1605,15 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   // and their env overrides below do not apply to it
   const bool pq8 = h->type == T_IVFPQ && h->nbits == 8;
   bool use_pre = pq8 && h->metric == M_L2 && h->pq_pre && h->term2.p;
-  if (use_pre) fam_floats = h->m * 256;  // LUT only, no rbuf
+  if (use_pre) {
+    p.mode = SCAN_PQ_PRE;
+    p.fam_floats = h->m * 256;  // LUT only, no rbuf
+  }
   // GLUT path: LUTs built once to HBM by k_pq_lut, scan stages them as
-  // coalesced float4 slabs. Auto at m >= 32: the in-kernel build
-  // re-reads the full m*256*dsub codebook from L2 per (query, probe)
-  // block and dominates the launch (measured 8.1 ms/launch at the
-  // configs[3] shape, ~125 GB/s of algorithmic code bytes).
+  // coalesced float4 slabs. The in-kernel build re-reads the full
+  // m*256*dsub codebook from L2 per (query, probe) block and dominates
+  // the launch at large m (measured 8.1 ms/launch at the configs[3]
+  // shape, ~125 GB/s of algorithmic code bytes).
   int glut_knob = h->pq_lut_global;
   if (const char *e = getenv("DFANN_PQ_LUT_GLOBAL"))  // experiment override
     glut_knob = atoi(e);
@@ -1609,18 +1625,32 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   // halved round-trip wins; =1 still forces the f32 variant for A/B.
   bool use_glut = pq8 && !use_pre && h->dsub <= 64 &&
                   (glut_knob == 1 || (glut_knob != 0 && lut_f16));
-  lut_f16 = lut_f16 && use_glut;
-  if (use_glut)  // LUT only, no rbuf; fam_floats is in FLOAT units
-    fam_floats = lut_f16 ? h->m * 128 : h->m * 256;
+  p.lut_f16 = lut_f16 && use_glut;
+  p.glut_qch = 0;
+  if (use_glut) {
+    p.mode = p.lut_f16 ? SCAN_PQ_GH : SCAN_PQ_G;
+    // LUT only, no rbuf; fam_floats is in FLOAT units
+    p.fam_floats = p.lut_f16 ? h->m * 128 : h->m * 256;
+    // chunk queries so the LUT buffer stays inside the budget (measured:
+    // bigger chunks win — concurrency beats LLC residency)
+    size_t row_b =
+        (size_t)nprobe * h->m * 256 * (p.lut_f16 ? 2 : 4);  // bytes/query
+    int lut_mb = h->pq_lut_mb;
+    if (const char *e = getenv("DFANN_PQ_LUT_MB"))  // experiment override
+      if (int v = atoi(e)) lut_mb = v;
+    int budget_mb = std::min(h->ws_mb, lut_mb);
+    p.glut_qch =
+        std::max<int64_t>(1, (int64_t)(((size_t)budget_mb << 20) / row_b));
+  }
   // segment fan (spec "scan_fan"): kept as an experiment knob — measured
   // NEGATIVE at the 10M SQ8 shape (per-block staging/extraction overhead
   // outweighs tail imbalance: 1936 -> 1339 GB/s at fan 8), so default 1.
-  int fan = h->type != T_IVFPQ ? h->scan_fan : 1;
+  p.fan = h->type != T_IVFPQ ? h->scan_fan : 1;
   // REGSEL extract scratch aliases the fam region (used only after the
   // scan, behind a barrier) -> max, not sum (kernels.hip ivf_scan_body)
-  size_t lds = rk ? std::max((size_t)fam_floats * 4, (size_t)REGSEL_LDS_BYTES)
-                  : (size_t)fam_floats * 4 + SEL_LDS_BYTES;
-  if (lds > 160 * 1024)
+  p.lds = rk ? std::max((size_t)p.fam_floats * 4, (size_t)REGSEL_LDS_BYTES)
+             : (size_t)p.fam_floats * 4 + SEL_LDS_BYTES;
+  if (p.lds > 160 * 1024)
     throw std::runtime_error("scan LDS over budget (m too large)");
   // big-LDS blocks (m=64 LUTs: ~69 KB -> 2 blocks/CU) run 512 threads so
   // the CU still holds 4 waves/SIMD (register path only; the LDS-buffer
@@ -1633,21 +1663,65 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   // 16 blocks/CU (+27% step); configs[3] f16 (32 KB) 256 = 5 blocks
   // (+8% over 384); SQ8 10M 128 threads +8%. The LDS-buffer selection
   // path keeps 256 (Sel capacity is sized for it).
-  unsigned scan_bs = 256;
+  p.scan_bs = 256;
   // round-2 addition: SQ scans drop to 64-thread blocks — measured +4%
   // on the config-5 125M SQ8 scan (2075 vs 1991 GB/s, gpurun_out/r2j_*)
   // and +6% at 10M; even more independent per-CU phases than the r1
   // 128-thread finding. IVF-Flat measured −5% at 64 (r2z_ivfflat), so
   // the drop is SQ-only.
-  if (rk) scan_bs = lds <= 16 * 1024 ? 128 : (lds <= 32 * 1024 ? 256 : 512);
-  if (rk && h->type == T_IVFSQ && lds <= 4 * 1024) scan_bs = 64;
+  if (rk)
+    p.scan_bs = p.lds <= 16 * 1024 ? 128 : (p.lds <= 32 * 1024 ? 256 : 512);
+  if (rk && h->type == T_IVFSQ && p.lds <= 4 * 1024) p.scan_bs = 64;
   if (const char *e = getenv("DFANN_SCAN_BS"))  // experiment override
-    if (int v = atoi(e)) scan_bs = (unsigned)((v / 64) * 64);
+    if (int v = atoi(e)) p.scan_bs = (unsigned)((v / 64) * 64);
+  return p;
+}
+
+// allow != nullptr: filtered search. The caller's id-space bitmap is
+// translated to CSR-position space (k_filter_id2pos, on every call — a
+// cache keyed on the caller's pointer would go stale silently) and the
+// FILT twins of the scans test one bit per row. Needs a finalized CSR.
+static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
+                           int nprobe, const int32_t *probes,
+                           const float *keys, int k, float *D, int64_t *I,
+                           hipStream_t stream,
+                           const uint32_t *allow = nullptr) {
+  const bool filt = allow != nullptr;
+  const bool ip = h->metric == M_IP;
+  const ScanPlan p = plan_scan(h, k, nprobe);
+  const scan_kern_t kern = scan_kernel(p.mode, ip, use_regsel(k), filt);
+  const bool use_pre = p.mode == SCAN_PQ_PRE;
+  const bool use_glut = p.mode == SCAN_PQ_G || p.mode == SCAN_PQ_GH;
+  const int fan = p.fan;
+
+  ScanArgs a = {};
+  a.cent = h->centroids.as<float>();
+  a.cb = h->codebooks.as<float>();
+  a.sq_vmin = h->sq_vmin.as<float>();
+  a.sq_scale = h->sq_scale.as<float>();
+  a.off = h->cr_off.as<int64_t>();
+  a.nprobe = nprobe;
+  a.d = h->d;
+  a.m = h->m;
+  a.dsub = h->dsub;
+  a.k = k;
+  a.stride = h->stride;
+  a.rlog = h->csr_arena.rlog;
+  a.fam_floats = p.fam_floats;
+  a.fan = fan;
+  if (filt) {
+    // outside the scan timing events: not counted in scan_ms
+    int64_t waves = (h->ntotal + 63) / 64;
+    h->filt_ws.ensure((size_t)waves * 8);
+    hipLaunchKernelGGL(k_filter_id2pos, dim3((unsigned)((waves + 3) / 4)),
+                       dim3(256), 0, stream, allow, h->cr_ids.as<int64_t>(),
+                       (long long)h->ntotal, h->filt_ws.as<unsigned>());
+    a.posbits = h->filt_ws.as<unsigned>();
+  }
   h->ws3.ensure((size_t)nq * nprobe * fan * k * 4);
   h->ws4.ensure((size_t)nq * nprobe * fan * k * 4);
-  cand_d = h->ws3.as<float>();
-  cand_p = h->ws4.as<unsigned>();
-  TimingEv e;
+  float *cand_d = h->ws3.as<float>();
+  unsigned *cand_p = h->ws4.as<unsigned>();
   if (use_pre) {
     // per-batch tables: q norms + term3 (counted as LUT-build time)
     TimingEv el;
@@ -1659,160 +1733,51 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                        0, stream, q, h->codebooks.as<float>(), nq, h->m,
                        h->dsub, h->term3_ws.as<float>());
     if (h->timing) h->ev_end(el, stream, h->ev_lut);
-    if (h->timing) e = h->ev_begin(stream);
-    auto pk = rk ? k_scan_pq_l2_pre_rk : k_scan_pq_l2_pre;
-    auto pk_f = rk ? k_scan_pq_l2_pre_rk_f : k_scan_pq_l2_pre_f;
-    if (filt)
-      hipLaunchKernelGGL(pk_f, dim3((unsigned)(nq * nprobe)), dim3(scan_bs),
-                         lds, stream, q, h->centroids.as<float>(),
-                         h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                         h->sq_scale.as<float>(), probes, keys,
-                         h->csr_arena.dev_table(stream),
-                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
-                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
-                         cand_p, fam_floats, h->term2.as<float>(),
-                         h->term3_ws.as<float>(), h->qn_ws.as<float>(),
-                         posbits);
-    else
-      hipLaunchKernelGGL(pk, dim3((unsigned)(nq * nprobe)), dim3(scan_bs), lds,
-                         stream, q, h->centroids.as<float>(),
-                         h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                         h->sq_scale.as<float>(), probes, keys,
-                         h->csr_arena.dev_table(stream),
-                         h->cr_off.as<int64_t>(),
-                         (int)nq, nprobe, h->d, h->m, h->dsub, k, h->stride,
-                         h->csr_arena.rlog,
-                         cand_d, cand_p, fam_floats, h->term2.as<float>(),
-                         h->term3_ws.as<float>(), h->qn_ws.as<float>());
-    if (h->timing) h->ev_end(e, stream, h->ev_scan);
-  } else if (use_glut) {
-    auto gk = lut_f16 ? (rk ? (ip ? k_scan_pq_ip_gh_rk : k_scan_pq_l2_gh_rk)
-                            : (ip ? k_scan_pq_ip_gh : k_scan_pq_l2_gh))
-                      : (rk ? (ip ? k_scan_pq_ip_g_rk : k_scan_pq_l2_g_rk)
-                            : (ip ? k_scan_pq_ip_g : k_scan_pq_l2_g));
-    auto gk_f =
-        lut_f16 ? (rk ? (ip ? k_scan_pq_ip_gh_rk_f : k_scan_pq_l2_gh_rk_f)
-                      : (ip ? k_scan_pq_ip_gh_f : k_scan_pq_l2_gh_f))
-                : (rk ? (ip ? k_scan_pq_ip_g_rk_f : k_scan_pq_l2_g_rk_f)
-                      : (ip ? k_scan_pq_ip_g_f : k_scan_pq_l2_g_f));
-    // chunk queries so the LUT buffer stays inside the budget (measured:
-    // bigger chunks win — concurrency beats LLC residency)
-    size_t row_b =
-        (size_t)nprobe * h->m * 256 * (lut_f16 ? 2 : 4);  // bytes/query
-    int lut_mb = h->pq_lut_mb;
-    if (const char *e = getenv("DFANN_PQ_LUT_MB"))  // experiment override
-      if (int v = atoi(e)) lut_mb = v;
-    int budget_mb = std::min(h->ws_mb, lut_mb);
-    int64_t qch =
-        std::max<int64_t>(1, (int64_t)(((size_t)budget_mb << 20) / row_b));
-    if (qch > nq) qch = nq;
-    h->pq_lut_ws.ensure((size_t)qch * row_b);
-    float *lutg = h->pq_lut_ws.as<float>();
-    int pad = h->dsub | 1;
-    size_t lut_lds = (size_t)(256 + PQ_LUT_QPT) * pad * 4;
-    for (int64_t q0 = 0; q0 < nq; q0 += qch) {
-      int64_t nqc = std::min<int64_t>(qch, nq - q0);
+    a.term2 = h->term2.as<float>();
+    a.term3 = h->term3_ws.as<float>();
+    a.qn = h->qn_ws.as<float>();
+  }
+  // one launch covers all queries, except on the GLUT path, which walks
+  // them in chunks of the LUT buffer: build the chunk's LUTs, scan it
+  int64_t qch = use_glut ? std::min(p.glut_qch, nq) : nq;
+  if (use_glut) {
+    h->pq_lut_ws.ensure((size_t)qch * nprobe * h->m * 256 *
+                        (p.lut_f16 ? 2 : 4));
+    a.glut = h->pq_lut_ws.as<float>();
+  }
+  for (int64_t q0 = 0; q0 < nq; q0 += qch) {
+    int64_t nqc = std::min<int64_t>(qch, nq - q0);
+    a.q = q + q0 * h->d;
+    a.probes = probes + q0 * nprobe;
+    a.keys = keys + q0 * nprobe;
+    a.nq = (int)nqc;
+    a.cand_d = cand_d + q0 * nprobe * fan * k;
+    a.cand_p = cand_p + q0 * nprobe * fan * k;
+    if (use_glut) {
       long long qpn = (long long)nqc * nprobe;
       dim3 lg((unsigned)((qpn + PQ_LUT_QPT - 1) / PQ_LUT_QPT),
               (unsigned)h->m);
+      int pad = h->dsub | 1;
+      size_t lut_lds = (size_t)(256 + PQ_LUT_QPT) * pad * 4;
       TimingEv el;
       if (h->timing) el = h->ev_begin(stream);
-      if (lut_f16) {
-        hipLaunchKernelGGL(k_pq_lut_f16, lg, dim3(256), lut_lds, stream,
-                           q + q0 * h->d, h->centroids.as<float>(),
-                           h->codebooks.as<float>(), probes + q0 * nprobe,
-                           (int)nqc, nprobe, h->d, h->m, h->dsub, ip ? 1 : 0,
-                           h->pq_lut_ws.as<__half>());
+      if (p.lut_f16) {
+        hipLaunchKernelGGL(k_pq_lut_f16, lg, dim3(256), lut_lds, stream, a.q,
+                           a.cent, a.cb, a.probes, a.nq, nprobe, h->d, h->m,
+                           h->dsub, ip ? 1 : 0, h->pq_lut_ws.as<__half>());
       } else {
-        hipLaunchKernelGGL(k_pq_lut, lg, dim3(256), lut_lds, stream,
-                           q + q0 * h->d, h->centroids.as<float>(),
-                           h->codebooks.as<float>(), probes + q0 * nprobe,
-                           (int)nqc, nprobe, h->d, h->m, h->dsub, ip ? 1 : 0,
-                           lutg);
+        hipLaunchKernelGGL(k_pq_lut, lg, dim3(256), lut_lds, stream, a.q,
+                           a.cent, a.cb, a.probes, a.nq, nprobe, h->d, h->m,
+                           h->dsub, ip ? 1 : 0, h->pq_lut_ws.as<float>());
       }
       if (h->timing) h->ev_end(el, stream, h->ev_lut);
-      if (h->timing) e = h->ev_begin(stream);
-      // persistent multi-pair variant (fp16 LUT + register top-k): a
-      // fixed grid strides over the (query, probe) pairs and prefetches
-      // the next pair's LUT during the current scan. MEASURED NEGATIVE
-      // at the headline shape (gpurun_out/r2s_pers*.json: scan 5.7 ->
-      // 6.9 ms at 2048 blocks — the hardware's cross-block overlap of
-      // 80k one-pair blocks beats the in-block pipeline), so OFF by
-      // default; DFANN_SCAN_PERS=1 re-enables for experiments.
-      // Bit-identical results either way (r2s_pers_check.log).
-      int pfn = 0;
-      long long qpn_c = (long long)nqc * nprobe;
-      const char *pers_env = getenv("DFANN_SCAN_PERS");
-      if (!filt && lut_f16 && rk && pers_env && atoi(pers_env) == 1) {
-        int lut_u4 = h->m * 32;  // m*256 halves / 8 per uint4
-        if (lut_u4 % (int)scan_bs == 0) {
-          int cand = lut_u4 / (int)scan_bs;
-          if (cand == 2 || cand == 4 || cand == 8 || cand == 16) pfn = cand;
-        }
-      }
-      if (pfn) {
-        auto pk = ip ? (pfn == 2 ? k_scan_pq_ip_ghp2
-                        : pfn == 4 ? k_scan_pq_ip_ghp4
-                        : pfn == 8 ? k_scan_pq_ip_ghp8 : k_scan_pq_ip_ghp16)
-                     : (pfn == 2 ? k_scan_pq_l2_ghp2
-                        : pfn == 4 ? k_scan_pq_l2_ghp4
-                        : pfn == 8 ? k_scan_pq_l2_ghp8 : k_scan_pq_l2_ghp16);
-        long long pb = 2048;
-        if (const char *e2 = getenv("DFANN_SCAN_PERS_BLOCKS"))
-          if (atoll(e2) > 0) pb = atoll(e2);
-        if (pb > qpn_c) pb = qpn_c;
-        hipLaunchKernelGGL(pk, dim3((unsigned)pb), dim3(scan_bs), lds, stream,
-                           q + q0 * h->d, h->centroids.as<float>(),
-                           h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                           h->sq_scale.as<float>(), probes + q0 * nprobe,
-                           keys + q0 * nprobe, h->csr_arena.dev_table(stream),
-                           h->cr_off.as<int64_t>(), (int)nqc, nprobe, h->d,
-                           h->m, h->dsub, k, h->stride, h->csr_arena.rlog,
-                           cand_d + q0 * nprobe * k, cand_p + q0 * nprobe * k,
-                           fam_floats, lutg);
-      } else if (filt) {
-        hipLaunchKernelGGL(gk_f, dim3((unsigned)(nqc * nprobe)), dim3(scan_bs),
-                           lds, stream, q + q0 * h->d, h->centroids.as<float>(),
-                           h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                           h->sq_scale.as<float>(), probes + q0 * nprobe,
-                           keys + q0 * nprobe, h->csr_arena.dev_table(stream),
-                           h->cr_off.as<int64_t>(), (int)nqc, nprobe, h->d,
-                           h->m, h->dsub, k, h->stride, h->csr_arena.rlog,
-                           cand_d + q0 * nprobe * k, cand_p + q0 * nprobe * k,
-                           fam_floats, lutg, posbits);
-      } else {
-        hipLaunchKernelGGL(gk, dim3((unsigned)(nqc * nprobe)), dim3(scan_bs),
-                           lds, stream, q + q0 * h->d, h->centroids.as<float>(),
-                           h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                           h->sq_scale.as<float>(), probes + q0 * nprobe,
-                           keys + q0 * nprobe, h->csr_arena.dev_table(stream),
-                           h->cr_off.as<int64_t>(), (int)nqc, nprobe, h->d,
-                           h->m, h->dsub, k, h->stride, h->csr_arena.rlog,
-                           cand_d + q0 * nprobe * k, cand_p + q0 * nprobe * k,
-                           fam_floats, lutg);
-      }
-      if (h->timing) h->ev_end(e, stream, h->ev_scan);
     }
-  } else {
+    TimingEv e;
     if (h->timing) e = h->ev_begin(stream);
-    if (filt)
-      hipLaunchKernelGGL(kern_f, dim3((unsigned)(nq * nprobe * fan)),
-                         dim3(scan_bs), lds, stream, q,
-                         h->centroids.as<float>(), h->codebooks.as<float>(),
-                         h->sq_vmin.as<float>(), h->sq_scale.as<float>(),
-                         probes, keys, h->csr_arena.dev_table(stream),
-                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
-                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
-                         cand_p, fam_floats, fan, posbits);
-    else
-      hipLaunchKernelGGL(kern, dim3((unsigned)(nq * nprobe * fan)),
-                         dim3(scan_bs), lds, stream, q,
-                         h->centroids.as<float>(), h->codebooks.as<float>(),
-                         h->sq_vmin.as<float>(), h->sq_scale.as<float>(),
-                         probes, keys, h->csr_arena.dev_table(stream),
-                         h->cr_off.as<int64_t>(), (int)nq, nprobe, h->d, h->m,
-                         h->dsub, k, h->stride, h->csr_arena.rlog, cand_d,
-                         cand_p, fam_floats, fan);
+    // (uploads the slab table after a CSR rebuild: inside the scan events)
+    a.codes = h->csr_arena.dev_table(stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nqc * nprobe * fan)),
+                       dim3(p.scan_bs), p.lds, stream, a);
     if (h->timing) h->ev_end(e, stream, h->ev_scan);
   }
   if (h->timing) {
@@ -1826,22 +1791,8 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   }
   TimingEv em;
   if (h->timing) em = h->ev_begin(stream);
-  if (merge_wave_ok(k, (int64_t)nprobe * fan * k)) {
-    hipLaunchKernelGGL(k_merge_cand_w, dim3((unsigned)((nq + 3) / 4)),
-                       dim3(256), 0, stream, cand_d, cand_p, nq,
-                       nprobe * fan * k, k, h->cr_ids.as<int64_t>(), ip ? 1 : 0,
-                       D, I);
-  } else if (use_regsel(k)) {
-    hipLaunchKernelGGL(k_merge_cand_rk, dim3((unsigned)nq), dim3(256),
-                       REGSEL_LDS_BYTES + 128, stream, cand_d, cand_p, nq,
-                       nprobe * fan * k, k, h->cr_ids.as<int64_t>(), ip ? 1 : 0,
-                       D, I);
-  } else {
-    hipLaunchKernelGGL(k_merge_cand, dim3((unsigned)nq), dim3(256),
-                       SEL_LDS_BYTES, stream, cand_d, cand_p, nq,
-                       nprobe * fan * k, k, h->cr_ids.as<int64_t>(), ip ? 1 : 0,
-                       D, I);
-  }
+  launch_merge_cand(stream, cand_d, cand_p, nq, nprobe * fan * k, k,
+                    h->cr_ids.as<int64_t>(), ip, D, I, true);
   if (h->timing) h->ev_end(em, stream, h->ev_merge);
   HIP_CHECK(hipGetLastError());
 }
@@ -1879,46 +1830,15 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
       gemm_keys(h, q + s * h->d, c, base, bn_rows, h->d, bn, qn + s,
                 ip ? 0 : 2, sc, stream);
       // winners layout: (nq, nch, k) — row stride nch*k
-      if (allow) {
-        if (use_regsel(k))
-          hipLaunchKernelGGL(k_topk_rows_rk_f, dim3((unsigned)c), dim3(256),
-                             REGSEL_LDS_BYTES, stream, sc, c,
-                             (long long)bn_rows, (long long)bn_rows, k,
-                             (unsigned)b0, (long long)(nch * k),
-                             wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
-                             allow);
-        else
-          hipLaunchKernelGGL(k_topk_rows_f, dim3((unsigned)c), dim3(256),
-                             SEL_LDS_BYTES, stream, sc, c, (long long)bn_rows,
-                             (long long)bn_rows, k, (unsigned)b0,
-                             (long long)(nch * k), wd + (s * nch + ci) * k,
-                             wp + (s * nch + ci) * k, allow);
-      } else if (use_regsel(k)) {
-        hipLaunchKernelGGL(k_topk_rows_rk, dim3((unsigned)c), dim3(256),
-                           REGSEL_LDS_BYTES, stream, sc, c, (long long)bn_rows,
-                           (long long)bn_rows, k, (unsigned)b0,
-                           (long long)(nch * k), wd + (s * nch + ci) * k,
-                           wp + (s * nch + ci) * k);
-      } else {
-        hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)c), dim3(256),
-                           SEL_LDS_BYTES, stream, sc, c, (long long)bn_rows,
-                           (long long)bn_rows, k, (unsigned)b0,
-                           (long long)(nch * k), wd + (s * nch + ci) * k,
-                           wp + (s * nch + ci) * k);
-      }
+      launch_topk_rows(stream, 256, sc, c, bn_rows, k, (unsigned)b0, nch * k,
+                       wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
+                       allow);
     }
   }
-  // merge chunk winners
-  if (use_regsel(k)) {
-    hipLaunchKernelGGL(k_merge_cand_rk, dim3((unsigned)nq), dim3(256),
-                       REGSEL_LDS_BYTES + 128, stream, wd, wp, nq,
-                       (int)(nch * k), k, (const int64_t *)nullptr,
-                       ip ? 1 : 0, D, I);
-  } else {
-    hipLaunchKernelGGL(k_merge_cand, dim3((unsigned)nq), dim3(256),
-                       SEL_LDS_BYTES, stream, wd, wp, nq, (int)(nch * k), k,
-                       (const int64_t *)nullptr, ip ? 1 : 0, D, I);
-  }
+  // merge chunk winners (flat ids are positions: no id table; block-per-
+  // query kernels only)
+  launch_merge_cand(stream, wd, wp, nq, (int)(nch * k), k, nullptr, ip, D, I,
+                    false);
   HIP_CHECK(hipGetLastError());
 }
 

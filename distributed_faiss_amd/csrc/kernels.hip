@@ -48,17 +48,6 @@ __device__ __forceinline__ uint8_t *slab_row_mut(
 }
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned uint32x4v;
-
-// 16-B non-temporal (evict-first) load; uint4 is a class type, so go
-// through the ext-vector form the builtin accepts
-__device__ __forceinline__ uint4 nt_load16(const void *p) {
-  uint32x4v v =
-      __builtin_nontemporal_load(reinterpret_cast<const uint32x4v *>(p));
-  union { uint32x4v v; uint4 u; } c;
-  c.v = v;
-  return c.u;
-}
 
 // allow-bitmap test (filtered search): uint32 words, bit i&31 of word
 // i>>5. Used with CSR positions (scan, bitmap from k_filter_id2pos) and
@@ -1017,119 +1006,6 @@ extern "C" __global__ __launch_bounds__(256) void k_coarse_reduce_rk(
 }
 
 // ---------------------------------------------------------------------------
-// 3-buffer glds ring variant of the 256² bf16 GEMM (cdna_hip_programming
-// §5 "Pipelining across barriers"): BK=32, three LDS buffers (96 KB), one
-// tile left IN FLIGHT across each barrier with counted s_waitcnt vmcnt —
-// raw s_barrier + lgkmcnt(0) instead of __syncthreads(), whose fence
-// would emit vmcnt(0) and drain the pipeline. This kernel runs at
-// 1 block/CU (the regime where the guide measures the span at +83% over
-// serial staging; the 2-buffer BK=64 k_gemm_bf16_256 is the +40% tier).
-// Requirements: K % 32 == 0 and NON-DIVERGENT staging — out-of-range
-// rows are address-CLAMPED (garbage lands in C rows/cols >= M/N, which
-// the epilogue guard discards) so every wave issues exactly 8 glds per
-// tile and the vmcnt counts are exact.
-// ---------------------------------------------------------------------------
-
-#define GB3_K 32
-
-extern "C" __global__ __launch_bounds__(512) void k_gemm_bf16_256_p3(
-    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
-    float *__restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
-    const float *__restrict__ qn, const float *__restrict__ bn, int mode) {
-  __shared__ unsigned short smem3[3][2][GB2_T][GB3_K];
-  int bi = blockIdx.y * GB2_T;
-  int bj = blockIdx.x * GB2_T;
-  int tid = threadIdx.x;
-  int lane = tid & 63, w = tid >> 6;
-  int wr = (w >> 2) * 128, wc = (w & 3) * 64;
-  f32x4 acc[8][4] = {};
-  int li = lane & 15;
-  int ke = (lane >> 4) * 8;
-
-  // 1024 16-B groups per operand (256 rows x 4), 8 waves x 2 x 64 lanes;
-  // 4 glds per thread per operand-pair iteration => 8 per tile
-#define GLDS3_STAGE(BUF, K0)                                                   \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) {                              \
-    int g = (w * 2 + i) * 64 + lane;                                           \
-    int r = g >> 2;                                                            \
-    int c8 = (g & 3) * 8;                                                      \
-    int c8s = c8 ^ ((r & 3) << 3); /* BK=32 source-side XOR swizzle */         \
-    int ra = bi + r < M ? bi + r : M - 1;                                      \
-    int rb = bj + r < N ? bj + r : N - 1;                                      \
-    unsigned short *ldst =                                                     \
-        &smem3[BUF][0][0][0] + ((size_t)(w * 2 + i) * 64) * 8;                 \
-    const unsigned short *ga = &A[(size_t)ra * lda + (K0) + c8s];              \
-    const unsigned short *gb = &B[(size_t)rb * ldb + (K0) + c8s];              \
-    __builtin_amdgcn_global_load_lds(                                          \
-        (const __attribute__((address_space(1))) unsigned int *)ga,            \
-        (__attribute__((address_space(3))) unsigned int *)ldst, 16, 0, 0);     \
-    unsigned short *ldstB =                                                    \
-        &smem3[BUF][1][0][0] + ((size_t)(w * 2 + i) * 64) * 8;                 \
-    __builtin_amdgcn_global_load_lds(                                          \
-        (const __attribute__((address_space(1))) unsigned int *)gb,            \
-        (__attribute__((address_space(3))) unsigned int *)ldstB, 16, 0, 0);    \
-  }
-
-#define GLDS3_MFMA(BUF)                                                        \
-  _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                           \
-    int rb = wc + tj * 16 + li;                                                \
-    int cbx = ke ^ ((rb & 3) << 3);                                            \
-    bf16x8 b0 = *reinterpret_cast<const bf16x8 *>(&smem3[BUF][1][rb][cbx]);    \
-    _Pragma("unroll") for (int ti = 0; ti < 8; ++ti) {                         \
-      int ra = wr + ti * 16 + li;                                              \
-      int ca = ke ^ ((ra & 3) << 3);                                           \
-      bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(&smem3[BUF][0][ra][ca]);   \
-      acc[ti][tj] =                                                            \
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[ti][tj],         \
-                                                  0, 0, 0);                    \
-    }                                                                          \
-  }
-
-#define RAW_BARRIER()                                                          \
-  do {                                                                         \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         \
-    __builtin_amdgcn_s_barrier();                                              \
-  } while (0)
-
-  const int T = K >> 5;  // K % 32 == 0 (host-guaranteed)
-  GLDS3_STAGE(0, 0)
-  if (T > 1) GLDS3_STAGE(1, GB3_K)
-  // buf0 landed (the 4 glds of buf1 may stay in flight)
-  if (T > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  RAW_BARRIER();
-  for (int t = 0; t < T; ++t) {
-    if (t + 2 < T) GLDS3_STAGE((t + 2) % 3, (t + 2) * GB3_K)
-    GLDS3_MFMA(t % 3)
-    if (t + 1 < T) {
-      // next buffer landed; the one after (if staged) stays in flight
-      if (t + 2 < T) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      RAW_BARRIER();
-    }
-  }
-
-  int rrow = (lane >> 4) * 4;
-#pragma unroll
-  for (int ti = 0; ti < 8; ++ti) {
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        int row = bi + wr + ti * 16 + rrow + rg;
-        int col = bj + wc + tj * 16 + li;
-        if (row < M && col < N)
-          C[(size_t)row * ldc + col] =
-              gemm_key(acc[ti][tj][rg], row, col, qn, bn, mode);
-      }
-    }
-  }
-#undef GLDS3_STAGE
-#undef GLDS3_MFMA
-#undef RAW_BARRIER
-}
-
-// ---------------------------------------------------------------------------
 
 extern "C" __global__ void k_assign_init(float *best_v, int *best_i, long long n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1438,9 +1314,8 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
   return acc;
 }
 
-template <int FAM, bool IS_IP, bool REGSEL, bool PRE = false,
-          bool GLUT = false, bool L16 = false, bool NT = false, int UR = 4,
-          bool FILT = false, bool N4 = false>
+template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
+          bool N4, bool FILT>
 __device__ void ivf_scan_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
@@ -1449,11 +1324,9 @@ __device__ void ivf_scan_body(
     const int64_t *__restrict__ off, int nq, int nprobe, int d, int m,
     int dsub, int k, int stride, int rlog, float *__restrict__ cand_d,
     unsigned *__restrict__ cand_p, int fam_floats,
-    const float *__restrict__ term2 = nullptr,
-    const float *__restrict__ term3 = nullptr,
-    const float *__restrict__ qn = nullptr, int fan = 1,
-    const float *__restrict__ glut = nullptr,
-    const unsigned *__restrict__ posbits = nullptr) {
+    const float *__restrict__ term2, const float *__restrict__ term3,
+    const float *__restrict__ qn, int fan, const float *__restrict__ glut,
+    const unsigned *__restrict__ posbits) {
   // FILT: posbits is the allow-bitmap in CSR-POSITION space (built per
   // call by k_filter_id2pos); a row whose bit is clear is never offered
   // to the selector. The word load is issued next to the row's code load
@@ -1661,6 +1534,8 @@ __device__ void ivf_scan_body(
       int g8 = threadIdx.x & 7, grp = threadIdx.x >> 3;  // 32 row-groups
       const bool onechunk = d <= 128;  // lane covers one 16-B chunk
       const int NG8 = blockDim.x >> 3;  // row groups per block
+      // row sets per iteration (8 measured 1.9 -> 1.1 TB/s)
+      constexpr int UR = 4;
       for (long long base = s0; base < s1; base += (long long)NG8 * UR) {
         if (!REGSEL) sel_guard(s, k, NG8 * UR);
         if (onechunk) {
@@ -1676,13 +1551,9 @@ __device__ void ivf_scan_body(
             ok4[u] = val4[u];
             if (FILT && val4[u]) ok4[u] = pos_allowed(posbits, pos);
             int t0 = g8 * 16;
-            // NT: non-temporal (evict-first) loads — the code stream is
-            // read exactly once per step, keep it out of L2's way
             wv4[u] = (val4[u] && t0 < d)
-                         ? (NT ? nt_load16(
-                                     slab_row(codes, rlog, pos, stride) + t0)
-                               : *reinterpret_cast<const uint4 *>(
-                                     slab_row(codes, rlog, pos, stride) + t0))
+                         ? *reinterpret_cast<const uint4 *>(
+                               slab_row(codes, rlog, pos, stride) + t0)
                          : uint4{0, 0, 0, 0};
           }
 #pragma unroll
@@ -1819,214 +1690,90 @@ __device__ void ivf_scan_body(
   }
 }
 
-#define INSTANTIATE_SCAN(NAME, FAM, IS_IP, REGSEL)                             \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,     \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,          \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan) {                             \
-    ivf_scan_body<FAM, IS_IP, REGSEL>(q, cent, cb, sq_vmin, sq_scale, probes,  \
-                                      keys, codes, off, nq, nprobe, d, m,      \
-                                      dsub, k, stride, rlog, cand_d, cand_p,   \
-                                      fam_floats, nullptr, nullptr, nullptr,   \
-                                      fan);                                    \
-  }
-
-#define INSTANTIATE_SCAN_PRE(NAME, REGSEL)                                     \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,     \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,          \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *term2,     \
-      const float *term3, const float *qn) {                                   \
-    ivf_scan_body<0, false, REGSEL, true>(q, cent, cb, sq_vmin, sq_scale,      \
-                                          probes, keys, codes, off, nq,        \
-                                          nprobe, d, m, dsub, k, stride, rlog, \
-                                          cand_d, cand_p, fam_floats, term2,   \
-                                          term3, qn);                          \
-  }
-
-INSTANTIATE_SCAN_PRE(k_scan_pq_l2_pre, false)
-INSTANTIATE_SCAN_PRE(k_scan_pq_l2_pre_rk, true)
-
-INSTANTIATE_SCAN(k_scan_pq_l2, 0, false, false)
-INSTANTIATE_SCAN(k_scan_pq_ip, 0, true, false)
-INSTANTIATE_SCAN(k_scan_ivfflat_l2, 1, false, false)
-INSTANTIATE_SCAN(k_scan_ivfflat_ip, 1, true, false)
-INSTANTIATE_SCAN(k_scan_sq8_l2, 2, false, false)
-INSTANTIATE_SCAN(k_scan_sq8_ip, 2, true, false)
-INSTANTIATE_SCAN(k_scan_sqf_l2, 3, false, false)
-INSTANTIATE_SCAN(k_scan_sqf_ip, 3, true, false)
-INSTANTIATE_SCAN(k_scan_pq_l2_rk, 0, false, true)
-INSTANTIATE_SCAN(k_scan_pq_ip_rk, 0, true, true)
-
-// GLUT variants: LUT staged from HBM (built by k_pq_lut) instead of
-// computed in the scan prologue — engine auto-selects at large m where
-// the in-kernel build's per-block codebook re-reads dominate.
-#define INSTANTIATE_SCAN_GLUT(NAME, IS_IP, REGSEL)                             \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,     \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,          \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *glut) {                   \
-    ivf_scan_body<0, IS_IP, REGSEL, false, true>(                              \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, 1, glut);                                                     \
-  }
-INSTANTIATE_SCAN_GLUT(k_scan_pq_l2_g, false, false)
-INSTANTIATE_SCAN_GLUT(k_scan_pq_ip_g, true, false)
-INSTANTIATE_SCAN_GLUT(k_scan_pq_l2_g_rk, false, true)
-INSTANTIATE_SCAN_GLUT(k_scan_pq_ip_g_rk, true, true)
-
-// fp16-LUT variants (pq_lut_f16): glut holds __half rows
-#define INSTANTIATE_SCAN_GLUT_H(NAME, IS_IP, REGSEL)                           \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,     \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,          \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *glut) {                   \
-    ivf_scan_body<0, IS_IP, REGSEL, false, true, true>(                        \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, 1, glut);                                                     \
-  }
-INSTANTIATE_SCAN_GLUT_H(k_scan_pq_l2_gh, false, false)
-INSTANTIATE_SCAN_GLUT_H(k_scan_pq_ip_gh, true, false)
-INSTANTIATE_SCAN_GLUT_H(k_scan_pq_l2_gh_rk, false, true)
-INSTANTIATE_SCAN_GLUT_H(k_scan_pq_ip_gh_rk, true, true)
-
 // ---------------------------------------------------------------------------
-// PERSISTENT fp16-GLUT scan (k <= 16 register selection): a fixed grid of
-// blocks loops over (query, probe) pairs with stride gridDim.x, and each
-// block PREFETCHES the NEXT pair's ADC table into registers while it
-// scans the current pair. Motivation (profiles/r01/pmc_sq_waits_1m.csv +
-// r1 ladder): at the headline shape a pair's list is ~190 rows — the
-// one-pair-per-block kernel is STAGING-dominated (stage 32 KB LUT, scan
-// ~12 KB of codes, die) and phase-converged (53% of wave cycles parked).
-// Here the LUT round-trip latency hides under the previous pair's scan +
-// top-k extraction, and block phases de-correlate naturally.
-//   * values are BIT-IDENTICAL to the one-pair kernel: same LUT bytes,
-//     same per-row accumulation order, same (dist, pos) selection.
-//   * PFN = LUT uint4 groups per thread (lut_bytes / blockDim / 16);
-//     host dispatches among the instantiations below and falls back to
-//     the one-pair kernel when the shape doesn't divide.
-//   * the RegTopK extraction scratch aliases the LDS LUT (as in
-//     ivf_scan_body); the prefetched registers rewrite the full LUT for
-//     the next pair after extraction's trailing barrier.
+// The scan kernels: one signature, one table.
+//
+// Every scan takes a ScanArgs by value. A kernel reads only the fields its
+// mode uses; scan_entry hands ivf_scan_body literal nullptr / 1 for the
+// rest, so each instantiation compiles against exactly the constants it
+// needs (fan is forced to 1 for PRE / GLUT, which never split a list).
+//
+// DFANN_SCAN_MODES is the table, one row per mode:
+//   row(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)
+// A row expands to k_scan_<NAME>_<l2|ip><SUFFIX>[_rk][_f]: metric x
+// {LDS-buffer selection, _rk register top-k (k <= 16)} x {plain, _f
+// filtered: FILT=true, rows tested against a.posbits}. XL2 rows have no
+// IP kernels (the precomputed tables are an L2 decomposition). The host
+// builds its [mode][ip][rk][filt] kernel table and the ScanMode enum from
+// the same list (dfann.hip scan_kernel), so a new scan dimension is one
+// row here plus its rule in plan_scan.
+//   PRE:  LUT = term2 - 2 * term3 from the precomputed tables
+//   GLUT: LUT staged from HBM (built by k_pq_lut) instead of computed in
+//         the scan prologue; L16: those rows are __half (pq_lut_f16)
+//   N4:   4-bit PQ (nbits=4), in-kernel fp32 LUT only
 // ---------------------------------------------------------------------------
+struct ScanArgs {
+  const float *q, *cent, *cb, *sq_vmin, *sq_scale;
+  const int *probes;
+  const float *keys;
+  const uint8_t *const *codes;
+  const int64_t *off;
+  int nq, nprobe, d, m, dsub, k, stride, rlog;
+  float *cand_d;
+  unsigned *cand_p;
+  int fam_floats;
+  const float *term2, *term3, *qn;  // PRE
+  int fan;                          // base modes (not PRE / GLUT)
+  const float *glut;                // GLUT
+  const unsigned *posbits;          // _f
+};
 
-template <bool IS_IP, int PFN>
-__device__ void scan_pq_ghp_body(
-    const float *__restrict__ q, const float *__restrict__ cent,
-    const float *__restrict__ cb, const float *__restrict__ sq_vmin,
-    const float *__restrict__ sq_scale, const int *__restrict__ probes,
-    const float *__restrict__ keys, const uint8_t *const *__restrict__ codes,
-    const int64_t *__restrict__ off, int nq, int nprobe, int d, int m,
-    int dsub, int k, int stride, int rlog, float *__restrict__ cand_d,
-    unsigned *__restrict__ cand_p, int fam_floats,
-    const float *__restrict__ glut) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *fam = reinterpret_cast<float *>(smem);
-  uint4 *lds4 = reinterpret_cast<uint4 *>(smem);
-  const int BS = blockDim.x;
-  long long qpn = (long long)nq * nprobe;
-  const int lut_u4 = PFN * BS;  // uint4 groups in one pair's fp16 LUT
-  const uint4 *lutg = reinterpret_cast<const uint4 *>(glut);
-
-  long long pair = blockIdx.x;
-  if (pair >= qpn) return;
-  // stage the first pair's LUT via global->LDS DMA
-  {
-    const uint4 *src = lutg + pair * (size_t)lut_u4;
-    for (int e = threadIdx.x; e < lut_u4; e += BS)
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int *)(src + e),
-          (__attribute__((address_space(3))) unsigned int *)(lds4 + e), 16, 0,
-          0);
-  }
-  uint4 pf[PFN];
-  for (; pair < qpn; pair += gridDim.x) {
-    long long nxt = pair + gridDim.x;
-    __syncthreads();  // staged/rewritten LUT visible (drains the glds)
-    // prefetch the next pair's LUT into registers: these loads fly
-    // together with the scan's row loads below
-    if (nxt < qpn) {
-      const uint4 *src = lutg + nxt * (size_t)lut_u4;
-#pragma unroll
-      for (int i = 0; i < PFN; ++i) pf[i] = src[i * BS + threadIdx.x];
-    }
-    // ---- scan this pair (same order/ops as ivf_scan_body REGSEL) ----
-    int L = probes[pair];
-    long long out_base = pair * k;
-    long long s0 = off[L], s1 = off[L + 1];
-    float bias = 0.f;
-    if (IS_IP) bias = -keys[pair];
-    if (s0 == s1) {
-      for (int j = threadIdx.x; j < k; j += BS) {
-        cand_d[out_base + j] = DFANN_FLT_MAX;
-        cand_p[out_base + j] = PAD_POS;
-      }
-    } else {
-      RegTopK<16> loc;
-      loc.init();
-      for (long long base = s0; base < s1; base += (long long)4 * BS) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          long long pos = base + (long long)u * BS + threadIdx.x;
-          if (pos < s1) {
-            const uint8_t *cp = slab_row(codes, rlog, pos, stride);
-            float acc = scan_row_dist<0, IS_IP, true>(cp, fam, d, m);
-            float dist = IS_IP ? -(bias + acc) : acc;
-            loc.push(dist, (unsigned)pos);
-          }
-        }
-      }
-      __syncthreads();  // all lanes done reading the LDS LUT
-      regtopk_block_extract<16>(loc, k, smem, cand_d + out_base,
-                                cand_p + out_base);
-    }
-    // install the prefetched LUT (extraction's trailing barrier ensures
-    // no lane still reads the old one; empty pairs never read it)
-    if (nxt < qpn) {
-      __syncthreads();  // pad-write case has no extraction barrier
-#pragma unroll
-      for (int i = 0; i < PFN; ++i) lds4[i * BS + threadIdx.x] = pf[i];
-    }
-  }
+template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
+          bool N4, bool FILT>
+__device__ __forceinline__ void scan_entry(const ScanArgs &a) {
+  ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT>(
+      a.q, a.cent, a.cb, a.sq_vmin, a.sq_scale, a.probes, a.keys, a.codes,
+      a.off, a.nq, a.nprobe, a.d, a.m, a.dsub, a.k, a.stride, a.rlog,
+      a.cand_d, a.cand_p, a.fam_floats, PRE ? a.term2 : nullptr,
+      PRE ? a.term3 : nullptr, PRE ? a.qn : nullptr,
+      (PRE || GLUT) ? 1 : a.fan, GLUT ? a.glut : nullptr,
+      FILT ? a.posbits : nullptr);
 }
 
-#define INSTANTIATE_SCAN_GHP(NAME, IS_IP, PFN)                                 \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,     \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,          \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *glut) {                   \
-    scan_pq_ghp_body<IS_IP, PFN>(q, cent, cb, sq_vmin, sq_scale, probes,       \
-                                 keys, codes, off, nq, nprobe, d, m, dsub, k,  \
-                                 stride, rlog, cand_d, cand_p, fam_floats,     \
-                                 glut);    \
+//  (MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)
+#define DFANN_SCAN_MODES(X, XL2)                                               \
+  X(PQ, pq, , 0, false, false, false, false)         /* PQ8 in-kernel LUT */   \
+  XL2(PQ_PRE, pq, _pre, 0, true, false, false, false) /* PQ8 precomputed */    \
+  X(PQ_G, pq, _g, 0, false, true, false, false)      /* PQ8 GLUT f32 */        \
+  X(PQ_GH, pq, _gh, 0, false, true, true, false)     /* PQ8 GLUT f16 */        \
+  X(PQ4, pq4, , 0, false, false, false, true)        /* 4-bit PQ */            \
+  X(IVFFLAT, ivfflat, , 1, false, false, false, false)                         \
+  X(SQ8, sq8, , 2, false, false, false, false)                                 \
+  X(SQF, sqf, , 3, false, false, false, false)       /* SQ fp16 */
+
+#define DFANN_SCAN_KERNEL(KNAME, FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT) \
+  extern "C" __global__ __launch_bounds__(512) void KNAME(ScanArgs a) {        \
+    scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT>(a);               \
   }
-
-INSTANTIATE_SCAN_GHP(k_scan_pq_l2_ghp2, false, 2)
-INSTANTIATE_SCAN_GHP(k_scan_pq_ip_ghp2, true, 2)
-INSTANTIATE_SCAN_GHP(k_scan_pq_l2_ghp4, false, 4)
-INSTANTIATE_SCAN_GHP(k_scan_pq_ip_ghp4, true, 4)
-INSTANTIATE_SCAN_GHP(k_scan_pq_l2_ghp8, false, 8)
-INSTANTIATE_SCAN_GHP(k_scan_pq_ip_ghp8, true, 8)
-INSTANTIATE_SCAN_GHP(k_scan_pq_l2_ghp16, false, 16)
-INSTANTIATE_SCAN_GHP(k_scan_pq_ip_ghp16, true, 16)
-
+#define DFANN_SCAN_METRIC(NAME, MET, SUFFIX, FAM, IS_IP, PRE, GLUT, L16, N4)   \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX, FAM, IS_IP, false, PRE,     \
+                    GLUT, L16, N4, false)                                      \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_f, FAM, IS_IP, false, PRE, \
+                    GLUT, L16, N4, true)                                       \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk, FAM, IS_IP, true, PRE, \
+                    GLUT, L16, N4, false)                                      \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk_f, FAM, IS_IP, true,    \
+                    PRE, GLUT, L16, N4, true)
+#define DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)         \
+  DFANN_SCAN_METRIC(NAME, l2, SUFFIX, FAM, false, PRE, GLUT, L16, N4)
+#define DFANN_SCAN_DEF(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)            \
+  DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)               \
+  DFANN_SCAN_METRIC(NAME, ip, SUFFIX, FAM, true, PRE, GLUT, L16, N4)
+DFANN_SCAN_MODES(DFANN_SCAN_DEF, DFANN_SCAN_DEF_L2)
+#undef DFANN_SCAN_DEF
+#undef DFANN_SCAN_DEF_L2
+#undef DFANN_SCAN_METRIC
+#undef DFANN_SCAN_KERNEL
 // ---------------------------------------------------------------------------
 // k_pq_lut: ADC lookup tables to HBM, one 256-entry row per (query,
 // probe, subspace) at out[(qp)*m*256 + j*256 + c] — the scan's GLUT
@@ -2205,163 +1952,6 @@ extern "C" __global__ __launch_bounds__(256) void k_pq_lut_f16(
     DFANN_PQ_LUT_DISPATCH(__half, true, false, out)
   }
 }
-#define INSTANTIATE_SCAN_NT(NAME, FAM, IS_IP, REGSEL)                          \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,                                                                  \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,         \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan) {              \
-    ivf_scan_body<FAM, IS_IP, REGSEL, false, false, false, true>(              \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, fan);                                                \
-  }
-INSTANTIATE_SCAN_NT(k_scan_sq8_l2_rk_nt, 2, false, true)
-INSTANTIATE_SCAN_NT(k_scan_sq8_ip_rk_nt, 2, true, true)
-
-#define INSTANTIATE_SCAN_U8(NAME, FAM, IS_IP, REGSEL)                          \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq,                                                                  \
-      int nprobe, int d, int m, int dsub, int k, int stride, int rlog,         \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan) {              \
-    ivf_scan_body<FAM, IS_IP, REGSEL, false, false, false, false, 8>(          \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, fan);                                                \
-  }
-INSTANTIATE_SCAN_U8(k_scan_sq8_l2_rk_u8, 2, false, true)
-INSTANTIATE_SCAN_U8(k_scan_sq8_ip_rk_u8, 2, true, true)
-
-INSTANTIATE_SCAN(k_scan_ivfflat_l2_rk, 1, false, true)
-INSTANTIATE_SCAN(k_scan_ivfflat_ip_rk, 1, true, true)
-INSTANTIATE_SCAN(k_scan_sq8_l2_rk, 2, false, true)
-INSTANTIATE_SCAN(k_scan_sq8_ip_rk, 2, true, true)
-INSTANTIATE_SCAN(k_scan_sqf_l2_rk, 3, false, true)
-INSTANTIATE_SCAN(k_scan_sqf_ip_rk, 3, true, true)
-
-// ---------------------------------------------------------------------------
-// filtered search (dfann_search_filtered): FILT=true twins of every scan
-// the dispatcher can pick from the spec — base (all families, fan),
-// PRE pair, GLUT g/gh set. Same signatures plus the trailing position
-// bitmap. The env-gated experiment kernels (nt / u8 / ghp) have no twin.
-// ---------------------------------------------------------------------------
-
-#define INSTANTIATE_SCAN_F(NAME, FAM, IS_IP, REGSEL)                           \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan,                \
-      const unsigned *posbits) {                                               \
-    ivf_scan_body<FAM, IS_IP, REGSEL, false, false, false, false, 4, true>(    \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, fan, nullptr, posbits);                              \
-  }
-INSTANTIATE_SCAN_F(k_scan_pq_l2_f, 0, false, false)
-INSTANTIATE_SCAN_F(k_scan_pq_ip_f, 0, true, false)
-INSTANTIATE_SCAN_F(k_scan_ivfflat_l2_f, 1, false, false)
-INSTANTIATE_SCAN_F(k_scan_ivfflat_ip_f, 1, true, false)
-INSTANTIATE_SCAN_F(k_scan_sq8_l2_f, 2, false, false)
-INSTANTIATE_SCAN_F(k_scan_sq8_ip_f, 2, true, false)
-INSTANTIATE_SCAN_F(k_scan_sqf_l2_f, 3, false, false)
-INSTANTIATE_SCAN_F(k_scan_sqf_ip_f, 3, true, false)
-INSTANTIATE_SCAN_F(k_scan_pq_l2_rk_f, 0, false, true)
-INSTANTIATE_SCAN_F(k_scan_pq_ip_rk_f, 0, true, true)
-INSTANTIATE_SCAN_F(k_scan_ivfflat_l2_rk_f, 1, false, true)
-INSTANTIATE_SCAN_F(k_scan_ivfflat_ip_rk_f, 1, true, true)
-INSTANTIATE_SCAN_F(k_scan_sq8_l2_rk_f, 2, false, true)
-INSTANTIATE_SCAN_F(k_scan_sq8_ip_rk_f, 2, true, true)
-INSTANTIATE_SCAN_F(k_scan_sqf_l2_rk_f, 3, false, true)
-INSTANTIATE_SCAN_F(k_scan_sqf_ip_rk_f, 3, true, true)
-
-#define INSTANTIATE_SCAN_PRE_F(NAME, REGSEL)                                   \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *term2,     \
-      const float *term3, const float *qn, const unsigned *posbits) {          \
-    ivf_scan_body<0, false, REGSEL, true, false, false, false, 4, true>(       \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, term2, term3, \
-        qn, 1, nullptr, posbits);                                              \
-  }
-INSTANTIATE_SCAN_PRE_F(k_scan_pq_l2_pre_f, false)
-INSTANTIATE_SCAN_PRE_F(k_scan_pq_l2_pre_rk_f, true)
-
-#define INSTANTIATE_SCAN_GLUT_F(NAME, IS_IP, REGSEL, L16)                      \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
-      float *cand_d, unsigned *cand_p, int fam_floats, const float *glut,      \
-      const unsigned *posbits) {                                               \
-    ivf_scan_body<0, IS_IP, REGSEL, false, true, L16, false, 4, true>(         \
-        q, cent, cb, sq_vmin, sq_scale, probes, keys, codes, off, nq, nprobe,  \
-        d, m, dsub, k, stride, rlog, cand_d, cand_p, fam_floats, nullptr,      \
-        nullptr, nullptr, 1, glut, posbits);                                   \
-  }
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_g_f, false, false, false)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_g_f, true, false, false)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_g_rk_f, false, true, false)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_g_rk_f, true, true, false)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_gh_f, false, false, true)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_f, true, false, true)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_l2_gh_rk_f, false, true, true)
-INSTANTIATE_SCAN_GLUT_F(k_scan_pq_ip_gh_rk_f, true, true, true)
-
-// ---------------------------------------------------------------------------
-// 4-bit PQ scans (nbits=4): FAM 0 with N4 set — in-kernel fp32 LUT only
-// (no PRE / GLUT / fp16 twins). Signatures are those of the base and the
-// filtered base kernels, so the dispatcher's `kern` / `kern_f` slots take
-// them unchanged.
-// ---------------------------------------------------------------------------
-
-#define INSTANTIATE_SCAN_N4(NAME, IS_IP, REGSEL)                               \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan) {              \
-    ivf_scan_body<0, IS_IP, REGSEL, false, false, false, false, 4, false,      \
-                  true>(q, cent, cb, sq_vmin, sq_scale, probes, keys, codes,   \
-                        off, nq, nprobe, d, m, dsub, k, stride, rlog, cand_d,  \
-                        cand_p, fam_floats, nullptr, nullptr, nullptr, fan);   \
-  }
-INSTANTIATE_SCAN_N4(k_scan_pq4_l2, false, false)
-INSTANTIATE_SCAN_N4(k_scan_pq4_ip, true, false)
-INSTANTIATE_SCAN_N4(k_scan_pq4_l2_rk, false, true)
-INSTANTIATE_SCAN_N4(k_scan_pq4_ip_rk, true, true)
-
-#define INSTANTIATE_SCAN_N4_F(NAME, IS_IP, REGSEL)                             \
-  extern "C" __global__ __launch_bounds__(512) void NAME(                      \
-      const float *q, const float *cent, const float *cb,                      \
-      const float *sq_vmin, const float *sq_scale, const int *probes,          \
-      const float *keys, const uint8_t *const *codes, const int64_t *off,      \
-      int nq, int nprobe, int d, int m, int dsub, int k, int stride, int rlog, \
-      float *cand_d, unsigned *cand_p, int fam_floats, int fan,                \
-      const unsigned *posbits) {                                               \
-    ivf_scan_body<0, IS_IP, REGSEL, false, false, false, false, 4, true,       \
-                  true>(q, cent, cb, sq_vmin, sq_scale, probes, keys, codes,   \
-                        off, nq, nprobe, d, m, dsub, k, stride, rlog, cand_d,  \
-                        cand_p, fam_floats, nullptr, nullptr, nullptr, fan,    \
-                        nullptr, posbits);                                     \
-  }
-INSTANTIATE_SCAN_N4_F(k_scan_pq4_l2_f, false, false)
-INSTANTIATE_SCAN_N4_F(k_scan_pq4_ip_f, true, false)
-INSTANTIATE_SCAN_N4_F(k_scan_pq4_l2_rk_f, false, true)
-INSTANTIATE_SCAN_N4_F(k_scan_pq4_ip_rk_f, true, true)
-
 // id-space allow-bitmap -> CSR-position-space bitmap: one thread per
 // position p, bit = allow[cr_ids[p]], packed with the 64-lane ballot;
 // lane 0 stores the wave's two words. The tail wave masks p >= ntotal to

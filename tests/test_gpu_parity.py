@@ -345,10 +345,10 @@ def test_pq_precomputed_table_path():
 def test_pq_glut_path_bitexact(m, metric):
     # HBM-LUT scan path (k_pq_lut + GLUT staging) vs the in-kernel LUT
     # build AND vs the oracle: k_pq_lut uses the identical sequential-t
-    # accumulation, so all three must agree BITWISE. m=32 also covers
-    # the auto-gate (pq_lut_global=-1 turns the path on at m >= 32);
-    # ws_mb=1 at m=8 forces the query-chunk loop (multiple k_pq_lut +
-    # scan launches per search).
+    # accumulation, so all three must agree BITWISE. The path is forced
+    # with pq_lut_global=1 (the default -1 turns it on only together
+    # with pq_lut_f16, the tolerance path); ws_mb=1 forces the
+    # query-chunk loop (multiple k_pq_lut + scan launches per search).
     d, nlist, per = 64, 8, 300
     cent, xb = _clustered(nlist, per, d, seed=41)
     rng = np.random.default_rng(42)

@@ -224,7 +224,7 @@ def test_search_equals_preassigned_and_env_overrides_are_ignored(monkeypatch):
     eng = _engine(_spec(case["d"], L2, 32, pq_lut_global=-1, pq_lut_mb=1), case)
     probes, keys = _coarse(eng, case)
     Do, Io = _oracle_topk(case, probes, keys, K_LDS)
-    for name in ("DFANN_PQ_LUT_GLOBAL", "DFANN_PQ_LUT_F16", "DFANN_SCAN_PERS"):
+    for name in ("DFANN_PQ_LUT_GLOBAL", "DFANN_PQ_LUT_F16"):
         monkeypatch.setenv(name, "1")
     for k in (K_REG, K_LDS):
         D, I = eng.search(case["q"], k)
