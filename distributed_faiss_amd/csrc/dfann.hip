@@ -357,6 +357,16 @@ struct dfann_index {
   double k_factor = 1.0;   // spec "k_factor" / dfann_set_k_factor
   SlabArena refine_arena;
   DevBuf rf_D, rf_I;
+  // OPQ pre-transform (faiss IndexPreTransform(OPQMatrix)):
+  // y = A x in front of an ivfpq that works entirely at d = d_out. d_in is
+  // the user-facing dimension (== d without a transform); the refine store
+  // and k_refine stay at d_in.
+  int d_in = 0;
+  bool opq = false;       // spec "opq"
+  bool opq_set = false;   // A learned / injected / loaded
+  int opq_niter = 16;     // spec "opq_niter" (faiss OPQMatrix: 50)
+  DevBuf opq_A, opq_At;   // (d_out, d_in) and its transpose, fp32
+  DevBuf opq_q, opq_x, opq_r;  // transformed queries / add chunk / decode
 
   // timing
   bool timing = false;
@@ -519,8 +529,12 @@ static void assign_rows(dfann_index *h, const float *x, int64_t n,
 
 static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
                           int d, int metric, uint64_t seed, float *cent_out,
-                          hipStream_t stream) {
-  const int NITER = 25;
+                          hipStream_t stream, bool hot_start = false,
+                          int niter = 25) {
+  // hot_start: cent_out already holds the centroids to refine (OPQ's
+  // per-round PQ retraining); niter: Lloyd iterations. The defaults are
+  // the plain training run.
+  const int NITER = niter;
   int64_t cap = (int64_t)kcent * (h ? h->max_ppc : 256);
   DevBuf xt_buf;
   const float *xt = x;
@@ -536,14 +550,17 @@ static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
   if (nt < kcent) throw std::runtime_error("kmeans: n < k");
 
   // init centroids
-  auto idx = pick_init(nt, kcent, seed);
   DevBuf idx_buf;
-  idx_buf.ensure(idx.size() * 8);
-  HIP_CHECK(hipMemcpyAsync(idx_buf.p, idx.data(), idx.size() * 8,
-                           hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_gather_rows, grid1d((int64_t)kcent * d), dim3(256), 0,
-                     stream, xt, idx_buf.as<int64_t>(), (long long)kcent, d,
-                     cent_out);
+  std::vector<int64_t> idx;
+  if (!hot_start) {
+    idx = pick_init(nt, kcent, seed);
+    idx_buf.ensure(idx.size() * 8);
+    HIP_CHECK(hipMemcpyAsync(idx_buf.p, idx.data(), idx.size() * 8,
+                             hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_gather_rows, grid1d((int64_t)kcent * d), dim3(256), 0,
+                       stream, xt, idx_buf.as<int64_t>(), (long long)kcent, d,
+                       cent_out);
+  }
   trace_point("kmeans:init", stream);
 
   DevBuf cn, asg, bestv, keys, sums, counts;
@@ -636,6 +653,242 @@ static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
 }
 
 // ---------------------------------------------------------------------------
+// OPQ pre-transform
+// ---------------------------------------------------------------------------
+
+// y (n x dout) = x (n x din) . A^T with A (dout x din): the one transform
+// launch (k_transform). Counted under gemm_ms / gemm_flops when `h` is given.
+static void run_transform(dfann_index *h, const float *A, int64_t n,
+                          const float *x, int din, int dout, float *y,
+                          hipStream_t stream) {
+  if (n == 0) return;
+  dim3 g((unsigned)((n + TF_T - 1) / TF_T), (unsigned)((dout + TF_T - 1) / TF_T));
+  TimingEv e;
+  if (h && h->timing) e = h->ev_begin(stream);
+  hipLaunchKernelGGL(k_transform, g, dim3(256), 0, stream, x, A, y,
+                     (long long)n, din, dout);
+  if (h && h->timing) {
+    h->ev_end(e, stream, h->ev_gemm);
+    h->gemm_flops += 2LL * n * din * dout;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+static void opq_require(const dfann_index *h) {
+  if (!h->opq) throw std::runtime_error("index has no opq transform");
+  if (!h->opq_set)
+    throw std::runtime_error("opq transform not set (train the index or call "
+                             "dfann_set_transform)");
+}
+
+// The query batch at d_out: q itself without a transform. The workspace
+// grows only when a larger batch is first seen (no sync, graph-capturable).
+static const float *opq_queries(dfann_index *h, int64_t nq, const float *q,
+                                hipStream_t stream) {
+  if (!h->opq || nq == 0) return q;
+  opq_require(h);
+  h->opq_q.ensure((size_t)nq * h->d * 4);
+  run_transform(h, h->opq_A.as<float>(), nq, q, h->d_in, h->d,
+                h->opq_q.as<float>(), stream);
+  return h->opq_q.as<float>();
+}
+
+// install A (device, d_out x d_in fp32) and derive its transpose
+static void opq_install(dfann_index *h, hipStream_t stream) {
+  h->opq_At.ensure((size_t)h->d * h->d_in * 4);
+  hipLaunchKernelGGL(k_opq_transpose, grid1d((int64_t)h->d * h->d_in),
+                     dim3(256), 0, stream, h->opq_A.as<float>(), h->d, h->d_in,
+                     h->opq_At.as<float>());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+  h->opq_set = true;
+}
+
+static double opq_read(const double *dev, hipStream_t stream) {
+  double v = 0.0;
+  HIP_CHECK(hipMemcpyAsync(&v, dev, 8, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  return v;
+}
+
+template <typename TA, typename TB>
+static void opq_dgemm(const TA *A, long long sai, long long sak, const TB *B,
+                      long long sbk, long long sbj, int R, int C, long long K,
+                      double alpha, double beta, const double *E, double *out,
+                      hipStream_t stream) {
+  dim3 g((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_opq_dgemm<TA, TB>), g, dim3(256), 0,
+                     stream, A, sai, sak, B, sbk, sbj, R, C, K, alpha, beta, E,
+                     out);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Orthonormal polar factor of X (R x C, R >= C, fp64, in place) by
+// Newton-Schulz: X <- 1.5 X - 0.5 X (X^T X) from X / |X|_F, until
+// max|X^T X - I| < 1e-10 (fp64 round-off of the C-term dot products is
+// ~1e-13). GEMM-only; the iteration count adapts to the singular-value
+// spread (each step lifts a small singular value by 1.5x).
+static void opq_polar(double *X, int R, int C, DevBuf &G, DevBuf &T,
+                      DevBuf &scal, hipStream_t stream) {
+  const long long total = (long long)R * C;
+  G.ensure((size_t)C * C * 8);
+  T.ensure((size_t)total * 8);
+  scal.ensure(16);
+  double *s = scal.as<double>();
+  hipLaunchKernelGGL(k_opq_sumsq, dim3(1), dim3(256), 0, stream, X, total, s);
+  double fro = std::sqrt(opq_read(s, stream));
+  if (!(fro > 0.0) || !std::isfinite(fro))
+    throw std::runtime_error("opq: polar factor of a zero / non-finite matrix");
+  hipLaunchKernelGGL(k_opq_axpby, grid1d(total), dim3(256), 0, stream, X,
+                     1.0 / fro, (const double *)nullptr, 0.0, total);
+  const int CAP = 200;
+  const double TOL = 1e-10;
+  double err = 0.0;
+  double *cur = X, *nxt = T.as<double>();
+  for (int it = 0; it <= CAP; ++it) {
+    // G = cur^T cur
+    opq_dgemm<double, double>(cur, 1, C, cur, C, 1, C, C, R, 1.0, 0.0, nullptr,
+                              G.as<double>(), stream);
+    hipLaunchKernelGGL(k_opq_maxdev, dim3(1), dim3(256), 0, stream,
+                       G.as<double>(), C, s);
+    err = opq_read(s, stream);
+    if (err < TOL) break;
+    if (it == CAP)
+      throw std::runtime_error(
+          "opq: Newton-Schulz polar iteration did not converge in " +
+          std::to_string(CAP) + " steps (max|XtX - I| = " +
+          std::to_string(err) + ")");
+    // nxt = 1.5 cur - 0.5 cur G
+    opq_dgemm<double, double>(cur, C, 1, G.as<double>(), C, 1, R, C, C, -0.5,
+                              1.5, cur, nxt, stream);
+    std::swap(cur, nxt);
+  }
+  if (cur != X)
+    HIP_CHECK(hipMemcpyAsync(X, cur, (size_t)total * 8,
+                             hipMemcpyDeviceToDevice, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// Learn A on the raw training rows (restates faiss OPQMatrix::train):
+// alternate a plain m x ksub PQ on Y = Xc A^T with the orthogonal
+// Procrustes update A^T = polar(Xc^T Yhat).
+static void opq_learn(dfann_index *h, int64_t n, const float *x,
+                      hipStream_t stream) {
+  const int di = h->d_in, dout = h->d, m = h->m, dsub = h->dsub;
+  const int ksub = pq_ksub(h);
+  // 1) strided subsample, centred (the mean is a training device only)
+  const int64_t nt = std::min<int64_t>(n, 65536);
+  if (nt < ksub)
+    throw std::runtime_error("opq: fewer training rows than PQ codewords");
+  DevBuf xc, mean;
+  xc.ensure((size_t)nt * di * 4);
+  mean.ensure((size_t)di * 8);
+  hipLaunchKernelGGL(k_gather_strided, grid1d(nt * di), dim3(256), 0, stream, x,
+                     (long long)n, (long long)nt, di, xc.as<float>());
+  hipLaunchKernelGGL(k_opq_colmean, dim3((unsigned)di), dim3(256), 0, stream,
+                     xc.as<float>(), (long long)nt, di, mean.as<double>());
+  hipLaunchKernelGGL(k_opq_center, grid1d(nt * di), dim3(256), 0, stream,
+                     xc.as<float>(), (long long)nt, di, mean.as<double>());
+  HIP_CHECK(hipGetLastError());
+  // 2) seeded Gaussian d_in x d_in (SplitMix64 + Box-Muller), orthonormalised
+  //    by the same polar routine; its first d_out columns are A^T
+  DevBuf Q, P, M, G, T, scal;
+  {
+    std::vector<double> g((size_t)di * di);
+    SplitMix64 rng(h->seed ^ 0x4F50514D41545258ULL);  // "OPQMATRX"
+    for (size_t i = 0; i < g.size(); i += 2) {
+      double u1 = ((double)(rng.next() >> 11) + 1.0) * (1.0 / 9007199254740992.0);
+      double u2 = (double)(rng.next() >> 11) * (1.0 / 9007199254740992.0);
+      double r = std::sqrt(-2.0 * std::log(u1));
+      g[i] = r * std::cos(6.283185307179586 * u2);
+      if (i + 1 < g.size()) g[i + 1] = r * std::sin(6.283185307179586 * u2);
+    }
+    Q.ensure(g.size() * 8);
+    HIP_CHECK(hipMemcpy(Q.p, g.data(), g.size() * 8, hipMemcpyHostToDevice));
+  }
+  opq_polar(Q.as<double>(), di, di, G, T, scal, stream);
+  P.ensure((size_t)di * dout * 8);
+  M.ensure((size_t)di * dout * 8);
+  hipLaunchKernelGGL(k_opq_take_cols, grid1d((int64_t)di * dout), dim3(256), 0,
+                     stream, Q.as<double>(), di, dout, P.as<double>());
+  Q.free();  // (columns of an orthonormal square matrix: no second pass)
+  h->opq_A.ensure((size_t)dout * di * 4);
+  h->opq_At.ensure((size_t)dout * di * 4);
+  auto store = [&]() {
+    hipLaunchKernelGGL(k_opq_store, grid1d((int64_t)di * dout), dim3(256), 0,
+                       stream, P.as<double>(), di, dout, h->opq_A.as<float>(),
+                       h->opq_At.as<float>());
+    HIP_CHECK(hipGetLastError());
+  };
+  store();
+  // 3) alternate
+  DevBuf y, yhat, sub, cb, cbn, best, bestv;
+  y.ensure((size_t)nt * dout * 4);
+  yhat.ensure((size_t)nt * dout * 4);
+  sub.ensure((size_t)nt * dsub * 4);
+  cb.ensure((size_t)m * ksub * dsub * 4);
+  cbn.ensure((size_t)ksub * 4);
+  best.ensure((size_t)nt * 4);
+  bestv.ensure((size_t)nt * 4);
+  int64_t chunk = std::max<int64_t>(1, ((int64_t)h->ws_mb << 20) / (ksub * 4));
+  chunk = std::min<int64_t>(chunk, nt);
+  h->ws1.ensure((size_t)chunk * ksub * 4);
+  for (int it = 0; it < h->opq_niter; ++it) {
+    run_transform(nullptr, h->opq_A.as<float>(), nt, xc.as<float>(), di, dout,
+                  y.as<float>(), stream);
+    for (int j = 0; j < m; ++j) {
+      float *cbj = cb.as<float>() + (size_t)j * ksub * dsub;
+      hipLaunchKernelGGL(k_subspace_slice, grid1d(nt * dsub), dim3(256), 0,
+                         stream, y.as<float>(), (long long)nt, dout, j * dsub,
+                         dsub, sub.as<float>());
+      // faiss niter_pq_0 / niter_pq (40 / 4): here the engine's 25 on the
+      // first round, then 4 hot-started
+      kmeans_device(h, sub.as<float>(), nt, ksub, dsub, M_L2,
+                    h->seed + 1000 + j, cbj, stream, it > 0, it == 0 ? 25 : 4);
+      // encode + decode
+      rownorms(cbj, ksub, dsub, cbn.as<float>(), stream);
+      hipLaunchKernelGGL(k_assign_init, grid1d(nt), dim3(256), 0, stream,
+                         bestv.as<float>(), best.as<int>(), nt);
+      for (int64_t s0 = 0; s0 < nt; s0 += chunk) {
+        int64_t c = std::min(chunk, nt - s0);
+        gemm_keys(nullptr, sub.as<float>() + s0 * dsub, c, cbj, ksub, dsub,
+                  cbn.as<float>(), nullptr, 1, h->ws1.as<float>(), stream);
+        hipLaunchKernelGGL(k_assign_rowblock, dim3((unsigned)c), dim3(256), 0,
+                           stream, h->ws1.as<float>(), c, (long long)ksub,
+                           (long long)ksub, 0, bestv.as<float>() + s0,
+                           best.as<int>() + s0);
+      }
+      hipLaunchKernelGGL(k_opq_decode_sub, grid1d(nt * dsub), dim3(256), 0,
+                         stream, best.as<int>(), cbj, (long long)nt, dout,
+                         j * dsub, dsub, ksub, yhat.as<float>());
+      HIP_CHECK(hipGetLastError());
+    }
+    // M = Xc^T Yhat (d_in x d_out), regularised with the previous rotation so
+    // that a null direction of the data keeps its orientation instead of
+    // stalling the iteration at a zero singular value
+    opq_dgemm<float, float>(xc.as<float>(), 1, di, yhat.as<float>(), dout, 1,
+                            di, dout, nt, 1.0, 0.0, nullptr, M.as<double>(),
+                            stream);
+    hipLaunchKernelGGL(k_opq_sumsq, dim3(1), dim3(256), 0, stream,
+                       M.as<double>(), (long long)di * dout, scal.as<double>());
+    double fro = std::sqrt(opq_read(scal.as<double>(), stream));
+    if (!std::isfinite(fro))
+      throw std::runtime_error("opq: non-finite training data");
+    if (!(fro > 0.0)) break;  // all-zero data: keep the initial rotation
+    hipLaunchKernelGGL(k_opq_axpby, grid1d((int64_t)di * dout), dim3(256), 0,
+                       stream, M.as<double>(), 1.0, P.as<double>(), 1e-6 * fro,
+                       (long long)di * dout);
+    opq_polar(M.as<double>(), di, dout, G, T, scal, stream);
+    std::swap(M.p, P.p);
+    std::swap(M.cap, P.cap);
+    store();
+    trace_point("opq:iter", stream);
+  }
+  HIP_CHECK(hipStreamSynchronize(stream));
+  h->opq_set = true;
+}
+
+// ---------------------------------------------------------------------------
 // create / train / add / finalize
 // ---------------------------------------------------------------------------
 
@@ -670,6 +923,34 @@ static dfann_index *create_from_spec(const std::string &js) {
   if (h->scan_fan < 1) h->scan_fan = 1;
   if (h->scan_fan > 16) h->scan_fan = 16;
   if (h->d <= 0) { delete h; throw std::runtime_error("bad dim"); }
+  h->d_in = h->d;
+  h->opq = json_int(js, "opq", 0) != 0;
+  if (h->opq) {
+    // faiss IndexPreTransform(OPQMatrix(d, M, d2), IndexIVFPQ): from here on
+    // h->d is the inner index dimension d_out (faiss extract_index_ivf sees
+    // the same: quantizer and PQ live at d2), h->d_in the caller's
+    int d_out = (int)json_int(js, "opq_dim", h->d_in);
+    h->opq_niter = (int)json_int(js, "opq_niter", 16);
+    std::string bad;
+    if (h->type != T_IVFPQ)
+      bad = "\"opq\" unsupported for index type '" + t + "' (ivfpq only)";
+    else if (d_out > h->d_in || d_out <= 0)
+      bad = "opq_dim=" + std::to_string(d_out) + " must be in 1..dim (" +
+            std::to_string(h->d_in) + ")";
+    else if (h->m <= 0 || d_out % h->m)
+      bad = "opq_dim=" + std::to_string(d_out) + " is not a multiple of m=" +
+            std::to_string(h->m);
+    else if (h->pq_pre)
+      bad = "\"opq\" with pq_precomputed unsupported (the term2 table is not "
+            "wired behind the transform)";
+    else if (h->opq_niter < 1)
+      bad = "opq_niter must be >= 1";
+    if (!bad.empty()) { delete h; throw std::runtime_error(bad); }
+    h->d = d_out;
+  } else if (json_int(js, "opq_dim", 0) != 0) {
+    delete h;
+    throw std::runtime_error("opq_dim given without \"opq\": 1");
+  }
   if (h->type != T_FLAT && h->type != T_HNSW && h->nlist <= 0) {
     delete h;
     throw std::runtime_error("bad nlist");
@@ -759,13 +1040,13 @@ static dfann_index *create_from_spec(const std::string &js) {
       delete h;
       throw std::runtime_error("k_factor must be >= 1");
     }
-    if (REFINE_LDS_BYTES(h->d) > 64 * 1024) {
+    if (REFINE_LDS_BYTES(h->d_in) > 64 * 1024) {
       delete h;
       throw std::runtime_error("refine: dim too large for the query stage");
     }
     int slab_mb = (int)json_int(js, "refine_slab_mb", 64);
     if (slab_mb < 1) slab_mb = 1;
-    h->refine_arena.init(round16(h->d * (h->refine == 1 ? 4 : 2)),
+    h->refine_arena.init(round16(h->d_in * (h->refine == 1 ? 4 : 2)),
                          (size_t)slab_mb << 20);
     h->refine_arena.zero_new = true;
   } else if (json_float(js, "k_factor", 1.0) < 1.0) {
@@ -1042,10 +1323,10 @@ static void refine_append(dfann_index *h, int64_t n, const float *x,
   // search ever has to
   uint8_t *const *tab = ra.dev_table_mut(stream);
   if (h->refine == 2) {
-    hipLaunchKernelGGL(k_refine_store_f16, grid1d(n * h->d), dim3(256), 0,
-                       stream, x, (long long)n, h->d, ra.stride, ra.rlog,
+    hipLaunchKernelGGL(k_refine_store_f16, grid1d(n * h->d_in), dim3(256), 0,
+                       stream, x, (long long)n, h->d_in, ra.stride, ra.rlog,
                        (long long)row0, tab);
-  } else if (ra.stride == 4 * h->d) {
+  } else if (ra.stride == 4 * h->d_in) {
     // fp32 rows with no pad: device-to-device copies, one per slab touched
     int64_t r = row0, left = n;
     const float *src = x;
@@ -1055,14 +1336,14 @@ static void refine_append(dfann_index *h, int64_t n, const float *x,
                   (size_t)(r & (ra.rps() - 1)) * ra.stride;
       HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)in_slab * ra.stride,
                                hipMemcpyDeviceToDevice, stream));
-      src += in_slab * h->d;
+      src += in_slab * h->d_in;
       r += in_slab;
       left -= in_slab;
     }
   } else {
     // d % 4 != 0: rows are padded to 16 B, so the copy is strided
-    hipLaunchKernelGGL(k_pack_rows, grid1d(n * h->d), dim3(256), 0, stream, x,
-                       (long long)n, h->d, ra.stride, ra.rlog, (long long)row0,
+    hipLaunchKernelGGL(k_pack_rows, grid1d(n * h->d_in), dim3(256), 0, stream, x,
+                       (long long)n, h->d_in, ra.stride, ra.rlog, (long long)row0,
                        tab);
   }
   HIP_CHECK(hipGetLastError());
@@ -1073,6 +1354,7 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream) {
   if (!h->trained) throw std::runtime_error("add on untrained index");
   if (n == 0) return;
+  if (h->opq) opq_require(h);
   if (h->type == T_HNSW) { hnsw_add(h, n, x, stream); return; }
   if (h->type == T_FLAT) {
     h->flat.grow_keep(((size_t)h->ntotal + n) * h->d * 4,
@@ -1093,10 +1375,19 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
   for (int64_t s = 0; s < n; s += CH) {
     int64_t c = std::min(CH, n - s);
     asg.ensure((size_t)c * 4);
-    assign_rows(h, x + s * h->d, c, asg.as<int>(), stream);
+    // OPQ: the chunk at d_out; the refine store keeps the raw d_in rows
+    const float *xs = x + s * h->d_in;
+    const float *xi = xs;
+    if (h->opq) {
+      h->opq_x.ensure((size_t)c * h->d * 4);
+      run_transform(h, h->opq_A.as<float>(), c, xs, h->d_in, h->d,
+                    h->opq_x.as<float>(), stream);
+      xi = h->opq_x.as<float>();
+    }
+    assign_rows(h, xi, c, asg.as<int>(), stream);
     int64_t row0 = (int64_t)h->h_pend_assign.size();
-    encode_chunk(h, c, x + s * h->d, asg.as<int>(), row0, stream);
-    if (h->refine) refine_append(h, c, x + s * h->d, stream);
+    encode_chunk(h, c, xi, asg.as<int>(), row0, stream);
+    if (h->refine) refine_append(h, c, xs, stream);
     size_t old = h->h_pend_assign.size();
     h->h_pend_assign.resize(old + c);
     HIP_CHECK(hipMemcpyAsync(h->h_pend_assign.data() + old, asg.p,
@@ -1920,13 +2211,13 @@ static void search_with_refine(dfann_index *h, int64_t nq, const float *q,
   base(kp, h->rf_D.as<float>(), h->rf_I.as<int64_t>());
   SlabArena &ra = h->refine_arena;
   const uint8_t *const *tab = ra.dev_table(stream);
-  const size_t lds = REFINE_LDS_BYTES(h->d);
+  const size_t lds = REFINE_LDS_BYTES(h->d_in);
   const bool ip = h->metric == M_IP;
   auto kern = h->refine == 2 ? (ip ? k_refine<__half, 0> : k_refine<__half, 1>)
                              : (ip ? k_refine<float, 0> : k_refine<float, 1>);
   hipLaunchKernelGGL(kern, dim3((unsigned)nq), dim3(256), lds, stream, q, tab,
                      ra.rlog, ra.stride, (long long)ra.rows,
-                     h->rf_I.as<int64_t>(), (long long)nq, kp, k, h->d, D, I);
+                     h->rf_I.as<int64_t>(), (long long)nq, kp, k, h->d_in, D, I);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1955,7 +2246,20 @@ extern "C" int dfann_destroy(dfann_index *h) {
 extern "C" int dfann_train(dfann_index *h, int64_t n, const float *x_dev,
                            dfann_stream stream) {
   API_BEGIN
-  train_impl(h, n, x_dev, (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  if (h->opq && !h->trained) {
+    // faiss IndexPreTransform::train: learn the transform on the raw rows
+    // (kept as is when one was injected), then train the inner index on
+    // the transformed set
+    if (!h->opq_set) opq_learn(h, n, x_dev, s);
+    DevBuf y;
+    y.ensure((size_t)std::max<int64_t>(n, 1) * h->d * 4);
+    run_transform(nullptr, h->opq_A.as<float>(), n, x_dev, h->d_in, h->d,
+                  y.as<float>(), s);
+    train_impl(h, n, y.as<float>(), s);
+    return 0;
+  }
+  train_impl(h, n, x_dev, s);
   API_END
 }
 
@@ -1971,9 +2275,11 @@ extern "C" int dfann_search(dfann_index *h, int64_t nq, const float *q_dev,
                             dfann_stream stream) {
   API_BEGIN
   hipStream_t s = (hipStream_t)stream;
+  // OPQ: transformed once; the refine stage re-ranks against the original
+  const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
-                       search_impl(h, nq, q_dev, kb, Db, Ib, s);
+                       search_impl(h, nq, qi, kb, Db, Ib, s);
                      });
   API_END
 }
@@ -1985,7 +2291,8 @@ extern "C" int dfann_coarse(dfann_index *h, int64_t nq, const float *q_dev,
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("coarse needs a trained IVF index");
   nprobe = std::min(nprobe, h->nlist);
-  coarse_impl(h, nq, q_dev, nprobe, probes_dev, keys_dev, (hipStream_t)stream);
+  const float *qi = opq_queries(h, nq, q_dev, (hipStream_t)stream);
+  coarse_impl(h, nq, qi, nprobe, probes_dev, keys_dev, (hipStream_t)stream);
   API_END
 }
 
@@ -1999,6 +2306,7 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
   hipStream_t s = (hipStream_t)stream;
+  const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
                        if (h->ntotal == 0) {
@@ -2006,7 +2314,7 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
                          return;
                        }
                        finalize_csr(h, s);
-                       scan_and_merge(h, nq, q_dev, nprobe, probes_dev,
+                       scan_and_merge(h, nq, qi, nprobe, probes_dev,
                                       keys_dev, kb, Db, Ib, s);
                      });
   API_END
@@ -2020,10 +2328,11 @@ extern "C" int dfann_search_filtered(dfann_index *h, int64_t nq,
   API_BEGIN
   check_filter(h, allow_bits_dev, nbits);
   hipStream_t s = (hipStream_t)stream;
+  const float *qi = opq_queries(h, nq, q_dev, s);
   // the filter applies in the base stage only: refine sees allowed ids
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
-                       search_impl(h, nq, q_dev, kb, Db, Ib, s,
+                       search_impl(h, nq, qi, kb, Db, Ib, s,
                                    allow_bits_dev);
                      });
   API_END
@@ -2041,6 +2350,7 @@ extern "C" int dfann_search_preassigned_filtered(
   if (k > 512) throw std::runtime_error("k > 512 unsupported");
   if (nq == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
                        if (h->ntotal == 0) {
@@ -2048,7 +2358,7 @@ extern "C" int dfann_search_preassigned_filtered(
                          return;
                        }
                        finalize_csr(h, s);
-                       scan_and_merge(h, nq, q_dev, nprobe, probes_dev,
+                       scan_and_merge(h, nq, qi, nprobe, probes_dev,
                                       keys_dev, kb, Db, Ib, s, allow_bits_dev);
                      });
   API_END
@@ -2062,21 +2372,31 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
   if (h->refine) {
     // a refine index returns the STORED rows, not the code decode
     hipStream_t s = (hipStream_t)stream;
+    const float *qi = opq_queries(h, nq, q_dev, s);
     search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                        [&](int kb, float *Db, int64_t *Ib) {
-                         search_impl(h, nq, q_dev, kb, Db, Ib, s);
+                         search_impl(h, nq, qi, kb, Db, Ib, s);
                        });
     if (nq == 0) return 0;
     SlabArena &ra = h->refine_arena;
     auto rk = h->refine == 2 ? k_refine_reconstruct<__half>
                              : k_refine_reconstruct<float>;
     hipLaunchKernelGGL(rk, dim3((unsigned)(nq * k)), dim3(64), 0, s, I_dev,
-                       (long long)(nq * k), h->d, ra.dev_table(s), ra.rlog,
+                       (long long)(nq * k), h->d_in, ra.dev_table(s), ra.rlog,
                        ra.stride, (long long)ra.rows, R_dev);
     HIP_CHECK(hipGetLastError());
     return 0;
   }
-  search_impl(h, nq, q_dev, k, D_dev, I_dev, (hipStream_t)stream);
+  const float *qi = opq_queries(h, nq, q_dev, (hipStream_t)stream);
+  search_impl(h, nq, qi, k, D_dev, I_dev, (hipStream_t)stream);
+  if (nq == 0) return 0;
+  // OPQ: decode at d_out, then rotate back with A^T (faiss
+  // VectorTransform::reverse_transform of an orthonormal matrix)
+  float *R_dec = R_dev;
+  if (h->opq) {
+    h->opq_r.ensure((size_t)nq * k * h->d * 4);
+    R_dec = h->opq_r.as<float>();
+  }
   int rtype;
   const float *flat_src = nullptr;
   if (h->type == T_FLAT) { rtype = 0; flat_src = h->flat.as<float>(); }
@@ -2091,8 +2411,11 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
                      h->id2pos.as<unsigned>(), h->cr_off.as<int64_t>(),
                      h->nlist, h->centroids.as<float>(),
                      h->codebooks.as<float>(), h->sq_vmin.as<float>(),
-                     h->sq_scale.as<float>(), R_dev);
+                     h->sq_scale.as<float>(), R_dec);
   HIP_CHECK(hipGetLastError());
+  if (h->opq)
+    run_transform(nullptr, h->opq_At.as<float>(), nq * k, R_dec, h->d,
+                  h->d_in, R_dev, (hipStream_t)stream);
   API_END
 }
 
@@ -2133,7 +2456,7 @@ extern "C" int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
 extern "C" int64_t dfann_ntotal(dfann_index *h) { return h->ntotal; }
 extern "C" int dfann_nlist(dfann_index *h) { return h->nlist; }
 extern "C" int dfann_is_trained(dfann_index *h) { return h->trained ? 1 : 0; }
-extern "C" int dfann_dim(dfann_index *h) { return h->d; }
+extern "C" int dfann_dim(dfann_index *h) { return h->d_in; }
 extern "C" const char *dfann_spec_json(dfann_index *h) {
   return h->spec_json.c_str();
 }
@@ -2196,6 +2519,10 @@ extern "C" int dfann_set_trained(dfann_index *h, const float *centroids_host,
                                  const float *vdiff_host) {
   API_BEGIN
   if (h->type == T_FLAT) { h->trained = true; return 0; }
+  if (h->opq && !h->opq_set)
+    throw std::runtime_error(
+        "set_trained on an opq index needs the transform first "
+        "(dfann_set_transform)");
   if (!centroids_host) throw std::runtime_error("centroids required");
   h->centroids.ensure((size_t)h->nlist * h->d * 4);
   h->cnorm.ensure((size_t)h->nlist * 4);
@@ -2228,6 +2555,53 @@ extern "C" int dfann_set_trained(dfann_index *h, const float *centroids_host,
   refresh_cent_bf16(h, 0);
   HIP_CHECK(hipDeviceSynchronize());
   h->trained = true;
+  API_END
+}
+
+// ---------------------------------------------------------------------------
+// OPQ transform exchange
+// ---------------------------------------------------------------------------
+
+extern "C" int dfann_transform_info(dfann_index *h, int64_t out[3]) {
+  API_BEGIN
+  out[0] = h->opq ? 1 : 0;
+  out[1] = h->d_in;
+  out[2] = h->d;
+  API_END
+}
+
+extern "C" int dfann_get_transform(dfann_index *h, float *A_host) {
+  API_BEGIN
+  opq_require(h);
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpy(A_host, h->opq_A.p, (size_t)h->d * h->d_in * 4,
+                      hipMemcpyDeviceToHost));
+  API_END
+}
+
+extern "C" int dfann_set_transform(dfann_index *h, const float *A_host) {
+  API_BEGIN
+  if (!h->opq) throw std::runtime_error("index has no opq transform");
+  if (!A_host) throw std::runtime_error("set_transform: null matrix");
+  if (h->ntotal > 0)
+    throw std::runtime_error(
+        "set_transform: the index already holds vectors encoded behind the "
+        "current transform");
+  HIP_CHECK(hipDeviceSynchronize());
+  h->opq_A.ensure((size_t)h->d * h->d_in * 4);
+  HIP_CHECK(hipMemcpy(h->opq_A.p, A_host, (size_t)h->d * h->d_in * 4,
+                      hipMemcpyHostToDevice));
+  opq_install(h, 0);
+  API_END
+}
+
+extern "C" int dfann_apply_transform(dfann_index *h, int64_t n,
+                                     const float *x_dev, float *y_dev,
+                                     dfann_stream stream) {
+  API_BEGIN
+  opq_require(h);
+  run_transform(h, h->opq_A.as<float>(), n, x_dev, h->d_in, h->d, y_dev,
+                (hipStream_t)stream);
   API_END
 }
 
@@ -2304,6 +2678,8 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
         dump_dev(f, h->centroids, (size_t)h->nlist * h->d * 4);
       if (h->type == T_IVFPQ)
         dump_dev(f, h->codebooks, (size_t)h->m * pq_ksub(h) * h->dsub * 4);
+      if (h->opq)  // only when the spec carries "opq": older files are as before
+        dump_dev(f, h->opq_A, (size_t)h->d * h->d_in * 4);
       if ((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq8) {
         dump_dev(f, h->sq_vmin, (size_t)h->d * 4);
         dump_dev(f, h->sq_vdiff, (size_t)h->d * 4);
@@ -2402,6 +2778,10 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
       rownorms(h->centroids.as<float>(), h->nlist, h->d, h->cnorm.as<float>(), 0);
       if (h->type == T_IVFPQ)
         load_dev(f, h->codebooks, (size_t)h->m * pq_ksub(h) * h->dsub * 4);
+      if (h->opq) {
+        load_dev(f, h->opq_A, (size_t)h->d * h->d_in * 4);
+        opq_install(h, 0);
+      }
       refresh_cent_bf16(h, 0);
       if (h->type == T_IVFSQ && h->sq8) {
         load_dev(f, h->sq_vmin, (size_t)h->d * 4);

@@ -2879,3 +2879,249 @@ __global__ __launch_bounds__(64) void k_refine_reconstruct(
       out[t] = reinterpret_cast<const float *>(row)[t];
   }
 }
+
+// ---------------------------------------------------------------------------
+// OPQ pre-transform: y = A x, A (d_out x d_in) fp32 row-major.
+// ---------------------------------------------------------------------------
+
+// The ONE transform kernel (add, every search entry, dfann_apply_transform,
+// the trainer's projection, and with A^T the reconstruct back-rotation).
+// Plain fp32 FMA, not MFMA: y[r][o] is a single fmaf chain over j = 0 ..
+// d_in-1 in ascending order, so a row's value depends on neither the batch
+// shape nor the row's position in it, and a signed-permutation A is exact.
+// 64 rows x 64 outputs per block, 4x4 per thread, 16-wide K steps (the zero
+// fill of a K tail adds fmaf(0, 0, acc) = acc).
+#define TF_T 64
+#define TF_K 16
+extern "C" __global__ __launch_bounds__(256) void k_transform(
+    const float *__restrict__ x, const float *__restrict__ A,
+    float *__restrict__ y, long long n, int d_in, int d_out) {
+  __shared__ float sX[TF_K][TF_T + 4];
+  __shared__ float sA[TF_K][TF_T + 4];
+  const long long r0 = (long long)blockIdx.x * TF_T;
+  const int o0 = blockIdx.y * TF_T;
+  const int tid = threadIdx.x;
+  const int tr = (tid >> 4) * 4, tc = (tid & 15) * 4;
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+  for (int k0 = 0; k0 < d_in; k0 += TF_K) {
+    for (int e = tid; e < TF_T * TF_K; e += 256) {
+      int r = e >> 4, c = e & 15;  // TF_K == 16
+      bool kin = k0 + c < d_in;
+      sX[c][r] = (kin && r0 + r < n) ? x[(r0 + r) * d_in + k0 + c] : 0.f;
+      sA[c][r] = (kin && o0 + r < d_out)
+                     ? A[(long long)(o0 + r) * d_in + k0 + c] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < TF_K; ++kk) {
+      float a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = sX[kk][tr + i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = sA[kk][tc + j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    long long r = r0 + tr + i;
+    if (r >= n) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (o0 + tc + j < d_out) y[r * d_out + o0 + tc + j] = acc[i][j];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// OPQ training (restates faiss OPQMatrix::train; dfann.hip opq_train). All
+// of it runs in fp64 with fixed-order reductions: same data + seed give a
+// bitwise-identical rotation.
+// ---------------------------------------------------------------------------
+
+// fixed-order block reduction of one double per thread (256 threads)
+__device__ __forceinline__ double opq_block_sum(double v, double *sh) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// column means of x (n x d), one block per column
+extern "C" __global__ __launch_bounds__(256) void k_opq_colmean(
+    const float *__restrict__ x, long long n, int d,
+    double *__restrict__ mean) {
+  __shared__ double sh[256];
+  const int c = blockIdx.x;
+  double acc = 0.0;
+  for (long long r = threadIdx.x; r < n; r += 256) acc += (double)x[r * d + c];
+  double s = opq_block_sum(acc, sh);
+  if (threadIdx.x == 0) mean[c] = s / (double)n;
+}
+
+// centring: x[r][c] -= mean[c]
+extern "C" __global__ void k_opq_center(float *__restrict__ x, long long n,
+                                        int d,
+                                        const double *__restrict__ mean) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = n * d;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x)
+    x[i] = (float)((double)x[i] - mean[i % d]);
+}
+
+// decode gather of one sub-space: yhat[r][j0 + t] = cb[best[r]][t]
+extern "C" __global__ void k_opq_decode_sub(const int *__restrict__ best,
+                                            const float *__restrict__ cb,
+                                            long long n, int d, int j0,
+                                            int dsub, int ksub,
+                                            float *__restrict__ yhat) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = n * dsub;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    long long r = i / dsub;
+    int t = (int)(i % dsub);
+    int c = best[r];
+    c = c < 0 ? 0 : (c >= ksub ? ksub - 1 : c);
+    yhat[r * d + j0 + t] = cb[(long long)c * dsub + t];
+  }
+}
+
+// C[i][j] = alpha * sum_k A(i,k) B(k,j) + beta * E[i][j]  (R x C, fp64
+// accumulation in ascending k), A(i,k) = A[i*sai + k*sak], B(k,j) =
+// B[k*sbk + j*sbj]: the strides give the transposed products (Xc^T Yhat,
+// X^T X) without a transpose pass; alpha / beta / E are the fused
+// Newton-Schulz epilogue X' = 1.5 X - 0.5 X (X^T X). E may be null
+// (beta ignored). 32x32 tile, 2x2 per thread.
+template <typename TA, typename TB>
+__global__ __launch_bounds__(256) void k_opq_dgemm(
+    const TA *__restrict__ A, long long sai, long long sak,
+    const TB *__restrict__ B, long long sbk, long long sbj, int R, int C,
+    long long K, double alpha, double beta, const double *__restrict__ E,
+    double *__restrict__ out) {
+  __shared__ double sA[16][33];
+  __shared__ double sB[16][33];
+  const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
+  const int tid = threadIdx.x;
+  const int ti = (tid >> 4) * 2, tj = (tid & 15) * 2;
+  double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
+  for (long long k0 = 0; k0 < K; k0 += 16) {
+    for (int e = tid; e < 32 * 16; e += 256) {
+      int p = e & 31, k = e >> 5;
+      bool kin = k0 + k < K;
+      sA[k][p] = (kin && i0 + p < R)
+                     ? (double)A[(long long)(i0 + p) * sai + (k0 + k) * sak]
+                     : 0.0;
+      sB[k][p] = (kin && j0 + p < C)
+                     ? (double)B[(k0 + k) * sbk + (long long)(j0 + p) * sbj]
+                     : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      double x0 = sA[k][ti], x1 = sA[k][ti + 1];
+      double y0 = sB[k][tj], y1 = sB[k][tj + 1];
+      a00 = fma(x0, y0, a00);
+      a01 = fma(x0, y1, a01);
+      a10 = fma(x1, y0, a10);
+      a11 = fma(x1, y1, a11);
+    }
+    __syncthreads();
+  }
+  const double acc[2][2] = {{a00, a01}, {a10, a11}};
+#pragma unroll
+  for (int di = 0; di < 2; ++di)
+#pragma unroll
+    for (int dj = 0; dj < 2; ++dj) {
+      int i = i0 + ti + di, j = j0 + tj + dj;
+      if (i < R && j < C) {
+        double v = alpha * acc[di][dj];
+        if (E) v += beta * E[(long long)i * C + j];
+        out[(long long)i * C + j] = v;
+      }
+    }
+}
+
+// single block: out[0] = sum x^2 (fixed order)
+extern "C" __global__ __launch_bounds__(256) void k_opq_sumsq(
+    const double *__restrict__ x, long long total, double *__restrict__ out) {
+  __shared__ double sh[256];
+  double acc = 0.0;
+  for (long long i = threadIdx.x; i < total; i += 256) acc += x[i] * x[i];
+  double s = opq_block_sum(acc, sh);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+// single block: out[0] = max |G - I| of a C x C matrix (NaN counts as +inf)
+extern "C" __global__ __launch_bounds__(256) void k_opq_maxdev(
+    const double *__restrict__ G, int C, double *__restrict__ out) {
+  __shared__ double sh[256];
+  double m = 0.0;
+  long long total = (long long)C * C;
+  for (long long i = threadIdx.x; i < total; i += 256) {
+    double v = fabs(G[i] - ((i / C) == (i % C) ? 1.0 : 0.0));
+    if (!(v <= m)) m = (v == v) ? v : 1e300;
+  }
+  sh[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s && sh[threadIdx.x + s] > sh[threadIdx.x])
+      sh[threadIdx.x] = sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+// x = a * x + b * y (y may be null)
+extern "C" __global__ void k_opq_axpby(double *__restrict__ x, double a,
+                                       const double *__restrict__ y, double b,
+                                       long long total) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x)
+    x[i] = a * x[i] + (y ? b * y[i] : 0.0);
+}
+
+// P (d_in x d_out, fp64, orthonormal columns) -> A = P^T (d_out x d_in)
+// and At = P (d_in x d_out), both fp32
+extern "C" __global__ void k_opq_store(const double *__restrict__ P, int d_in,
+                                       int d_out, float *__restrict__ A,
+                                       float *__restrict__ At) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = (long long)d_in * d_out;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    int r = (int)(i / d_out), c = (int)(i % d_out);
+    float v = (float)P[i];
+    At[i] = v;
+    A[(long long)c * d_in + r] = v;
+  }
+}
+
+// first `cols` columns of a square (d x d) matrix -> (d x cols)
+extern "C" __global__ void k_opq_take_cols(const double *__restrict__ Q, int d,
+                                           int cols, double *__restrict__ P) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = (long long)d * cols;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x)
+    P[i] = Q[(i / cols) * d + (i % cols)];
+}
+
+// fp32 transpose (set_transform: At from an injected A)
+extern "C" __global__ void k_opq_transpose(const float *__restrict__ A,
+                                           int rows, int cols,
+                                           float *__restrict__ At) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = (long long)rows * cols;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x)
+    At[(i % cols) * rows + (i / cols)] = A[i];
+}

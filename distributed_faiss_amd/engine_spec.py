@@ -10,6 +10,8 @@
 #   §6d), sq_type ("fp16"|"8bit"), nprobe, seed
 #   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
 #   (faiss IndexRefineFlat / IndexRefine)
+#   opq (1), opq_dim, opq_niter: learned orthonormal pre-transform in front
+#   of ivfpq (faiss IndexPreTransform(OPQMatrix))
 #
 # Behavioral quirks kept on purpose (SURVEY.md §2 quirk list):
 #   * builder "flat" ALWAYS builds an inner-product flat index, ignoring
@@ -71,7 +73,7 @@ def _builder_spec(cfg: IndexCfg) -> dict:
             nbits=int(cfg.extra.get("bits_per_vector", 8)),
             nprobe=1,
         )
-        return _apply_refine(cfg, spec)
+        return _apply_refine(cfg, _apply_opq(cfg, spec))
     if t == "ivfsq":
         # reference index.py:63-68 — QT_fp16
         spec.update(type="ivfsq", nlist=int(cfg.centroids), sq_type="fp16")
@@ -100,8 +102,11 @@ def _builder_spec(cfg: IndexCfg) -> dict:
 
 # optional third component, PQ / SQ bases only: faiss IndexRefineFlat
 # ("RFlat") and IndexRefine over an fp16 scalar quantizer ("Refine(SQfp16)")
+# optional first component, PQ bases only: faiss OPQMatrix ("OPQ<m>" or
+# "OPQ<m>_<d_out>")
 _FACTORY_RE = re.compile(
-    r"^IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQfp16)"
+    r"^(?:OPQ(?P<opq_m>\d+)(?:_(?P<opq_d>\d+))?,)?"
+    r"IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQfp16)"
     r"(?:,(RFlat|Refine\(SQfp16\)))?)$")
 _FACTORY_REFINE = {"RFlat": "fp32", "Refine(SQfp16)": "fp16"}
 # "PQ<m>x<b>": bits per sub-quantizer code; "PQ<m>" is faiss's default 8
@@ -109,6 +114,21 @@ PQ_NBITS_SUPPORTED = (4, 8)
 
 # Refine keys of cfg.extra. NOT perf knobs: they change results.
 REFINE_KEYS = ("refine", "k_factor")
+# OPQ keys of cfg.extra (builder knnlm; "opq_niter" also with an OPQ factory
+# string). Result-changing like REFINE_KEYS, not perf knobs.
+OPQ_KEYS = ("opq", "opq_dim", "opq_niter")
+
+
+def _apply_opq(cfg: IndexCfg, spec: dict) -> dict:
+    """cfg.extra["opq"] (truthy), ["opq_dim"], ["opq_niter"] on the ivfpq
+    builder; the engine checks m | opq_dim <= dim."""
+    if cfg.extra.get("opq"):
+        spec["opq"] = 1
+        if "opq_dim" in cfg.extra:
+            spec["opq_dim"] = int(cfg.extra["opq_dim"])
+        if "opq_niter" in cfg.extra:
+            spec["opq_niter"] = int(cfg.extra["opq_niter"])
+    return spec
 
 
 def _apply_refine(cfg: IndexCfg, spec: dict) -> dict:
@@ -138,28 +158,47 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if not mm:
         raise NotImplementedError(
             f"factory string {s!r} not supported; supported: Flat, IVFn,Flat, "
-            "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQfp16, and "
-            "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16)"
+            "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQfp16, "
+            "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16), and "
+            "the PQ forms preceded by OPQm, or OPQm_d, (same m)"
         )
-    nlist = int(mm.group(1))
-    kind = mm.group(2) or mm.group(3)
+    opq_m = mm.group("opq_m")
+    nlist = int(mm.group(3))
+    kind = mm.group(4) or mm.group(5)
+    if opq_m is not None and not kind.startswith("PQ"):
+        raise NotImplementedError(
+            f"factory string {s!r}: OPQ is supported in front of IVFn,PQm "
+            "only, not Flat / SQ8 / SQfp16"
+        )
     if kind == "Flat":
         spec.update(type="ivf_flat", nlist=nlist)
         return spec
     if kind.startswith("PQ"):
-        nbits = int(mm.group(5)) if mm.group(5) else 8
+        nbits = int(mm.group(7)) if mm.group(7) else 8
         if nbits not in PQ_NBITS_SUPPORTED:
             raise NotImplementedError(
                 f"factory string {s!r}: PQ with {nbits} bits per code not "
                 f"supported; supported: {list(PQ_NBITS_SUPPORTED)}"
             )
-        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(4)), nbits=nbits)
+        spec.update(type="ivfpq", nlist=nlist, m=int(mm.group(6)), nbits=nbits)
+        if opq_m is not None:
+            if int(opq_m) != spec["m"]:
+                raise NotImplementedError(
+                    f"factory string {s!r}: OPQ{opq_m} in front of "
+                    f"PQ{spec['m']} not supported (the OPQ m must equal the "
+                    "PQ m)"
+                )
+            spec["opq"] = 1
+            if mm.group("opq_d"):
+                spec["opq_dim"] = int(mm.group("opq_d"))
+            if "opq_niter" in cfg.extra:
+                spec["opq_niter"] = int(cfg.extra["opq_niter"])
     elif kind == "SQ8":
         spec.update(type="ivfsq", nlist=nlist, sq_type="8bit")
     else:
         spec.update(type="ivfsq", nlist=nlist, sq_type="fp16")
-    if mm.group(6):
-        spec["refine"] = _FACTORY_REFINE[mm.group(6)]
+    if mm.group(8):
+        spec["refine"] = _FACTORY_REFINE[mm.group(8)]
         if "k_factor" in cfg.extra:
             spec["k_factor"] = float(cfg.extra["k_factor"])
     return spec

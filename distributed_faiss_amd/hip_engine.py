@@ -97,6 +97,11 @@ def load_lib():
     lib.dfann_get_codebooks.argtypes = [c.c_void_p, c.c_void_p]
     lib.dfann_get_sq_params.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p]
     lib.dfann_set_trained.argtypes = [c.c_void_p] + [c.c_void_p] * 4
+    lib.dfann_get_transform.argtypes = [c.c_void_p, c.c_void_p]
+    lib.dfann_set_transform.argtypes = [c.c_void_p, c.c_void_p]
+    lib.dfann_apply_transform.argtypes = [c.c_void_p, c.c_int64, c.c_void_p,
+                                          c.c_void_p, c.c_void_p]
+    lib.dfann_transform_info.argtypes = [c.c_void_p, c.c_void_p]
     lib.dfann_save.argtypes = [c.c_void_p, c.c_char_p]
     lib.dfann_load.argtypes = [c.c_char_p, P(c.c_void_p)]
     lib.dfann_merge_topk.argtypes = [c.c_int64, c.c_int, c.c_int, c.c_void_p,
@@ -359,7 +364,8 @@ class HipEngine:
     # -- introspection / artifacts ----------------------------------------
 
     def get_centroids(self):
-        out = np.empty((self.nlist, self.d), dtype=np.float32)
+        # (nlist, d_out) behind an OPQ transform: the inner index's
+        out = np.empty((self.nlist, self.d_inner), dtype=np.float32)
         _check(self.lib, self.lib.dfann_get_centroids(
             self.h, out.ctypes.data_as(ctypes.c_void_p)))
         return out
@@ -367,7 +373,7 @@ class HipEngine:
     def _pq_shape(self):
         """(m, ksub, dsub) of the PQ codebooks; ksub = 1 << nbits."""
         m = int(self.spec["m"])
-        return m, 1 << int(self.spec.get("nbits", 8)), self.d // m
+        return m, 1 << int(self.spec.get("nbits", 8)), self.d_inner // m
 
     def get_codebooks(self):
         out = np.empty(self._pq_shape(), dtype=np.float32)
@@ -424,6 +430,61 @@ class HipEngine:
             cb.ctypes.data_as(ctypes.c_void_p) if cb is not None else None,
             vm.ctypes.data_as(ctypes.c_void_p) if vm is not None else None,
             vd.ctypes.data_as(ctypes.c_void_p) if vd is not None else None))
+
+    # -- OPQ pre-transform ---------------------------------
+
+    def transform_info(self):
+        """(on, d_in, d_out): on 0|1; d_in == d_out == d without a
+        transform. `d` stays the user-facing dimension d_in."""
+        out = np.empty(3, dtype=np.int64)
+        _check(self.lib, self.lib.dfann_transform_info(
+            self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return tuple(int(v) for v in out)
+
+    @property
+    def d_inner(self):
+        """Dimension of the inner index (centroids, codebooks): d_out
+        behind an OPQ transform, d otherwise."""
+        return self.transform_info()[2]
+
+    def get_transform(self):
+        """The OPQ matrix A, (d_out, d_in) float32 (y = A x)."""
+        _on, d_in, d_out = self.transform_info()
+        out = np.empty((d_out, d_in), dtype=np.float32)
+        _check(self.lib, self.lib.dfann_get_transform(
+            self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def set_transform(self, A):
+        """Inject A, (d_out, d_in) float32 — artifact exchange, like
+        set_trained (which needs the transform first on an OPQ index)."""
+        _on, d_in, d_out = self.transform_info()
+        A = np.ascontiguousarray(A, dtype=np.float32)
+        if A.shape != (d_out, d_in):
+            raise ValueError(
+                f"transform: expected shape {(d_out, d_in)}, got {A.shape}")
+        _check(self.lib, self.lib.dfann_set_transform(
+            self.h, A.ctypes.data_as(ctypes.c_void_p)))
+
+    def apply_transform(self, x):
+        """y = x A^T through the engine's own transform kernel (the one
+        add and search run): numpy (n, d_in) -> (n, d_out)."""
+        torch = _torch()
+        xt = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+        return self.apply_transform_dev(xt).cpu().numpy()
+
+    def apply_transform_dev(self, xt, out=None):
+        torch = _torch()
+        _on, d_in, d_out = self.transform_info()
+        if xt.dim() != 2 or xt.shape[1] != d_in:
+            raise ValueError(f"apply_transform: expected (n, {d_in}) rows")
+        if out is None:
+            out = torch.empty((xt.shape[0], d_out), dtype=torch.float32,
+                              device="cuda")
+        _check(self.lib, self.lib.dfann_apply_transform(
+            self.h, xt.shape[0], ctypes.c_void_p(xt.data_ptr()),
+            ctypes.c_void_p(out.data_ptr()), self._stream(torch)))
+        return out
 
     # -- refine store introspection (test plumbing) ------------------------
 

@@ -39,6 +39,22 @@
  *    (k_factor travels as float32: 10 * 1.6f re-ranks 16, not 17).
  *  - refine needs dim <= 15360 (the query is staged in LDS next to the
  *    512-entry sort buffer).
+ *
+ * OPQ pre-transform ("opq": 1, ivfpq only): the index is
+ * faiss IndexPreTransform(OPQMatrix(dim, m, opq_dim), IndexIVFPQ). A linear
+ * map y = A x, A (opq_dim, dim) fp32 row-major with orthonormal rows and no
+ * bias, runs in front of an ivfpq that works entirely at opq_dim: callers
+ * pass and receive dim-wide vectors (dfann_dim, dfann_search_reconstruct,
+ * the refine store), while everything faiss extract_index_ivf would reach
+ * lives at opq_dim — dfann_get_centroids is (nlist, opq_dim), the
+ * codebooks (m, 1 << nbits, opq_dim / m). The transform always runs in
+ * fp32 (whatever "coarse_bf16" says) in one kernel whose per-row result
+ * does not depend on the batch it came in, and counts under gemm_ms /
+ * gemm_flops. Deviations from faiss OPQMatrix::train: 16 outer iterations
+ * by default ("opq_niter"; faiss 50), k-means 25 iterations on the first
+ * round and 4 hot-started after (faiss 40 / 4), at most 65536 strided
+ * training rows, and the polar factor by Newton-Schulz in fp64 on the GPU
+ * instead of an SVD.
  */
 #ifndef DFANN_H
 #define DFANN_H
@@ -73,6 +89,12 @@ typedef void *dfann_stream;             /* hipStream_t */
  * float >= 1 (default 1.0, see Limits for k'); "refine_slab_mb": slab size
  * of the raw store (default 64). "refine" on flat / ivf_flat / hnswsq and
  * k_factor < 1 are errors.
+ * OPQ, "ivfpq" only (see the header comment): "opq": 1 turns the
+ * pre-transform on; "opq_dim": d_out (default dim; m must divide it and it
+ * must be <= dim); "opq_niter": outer training iterations (default 16).
+ * Errors naming the key: "opq" on another index type, opq_dim > dim,
+ * opq_dim % m != 0, and "opq" with "pq_precomputed" (the term2 table is
+ * not wired behind the transform).
  * Replaces: faiss.IndexFlatIP/IndexFlatL2 (ref index.py:28-30,94),
  * faiss.IndexIVFFlat (ref index.py:38), faiss.IndexIVFPQ (ref
  * index.py:46), faiss.IndexIVFScalarQuantizer + QT_fp16/QT_8bit (ref
@@ -83,7 +105,11 @@ int dfann_destroy(dfann_index *h);
 /* --- build path ------------------------------------------------------- */
 
 /* Replaces faiss `Index.train` at ref index.py:217 (k-means coarse
- * quantizer; + per-subspace PQ codebooks / SQ ranges on residuals). */
+ * quantizer; + per-subspace PQ codebooks / SQ ranges on residuals). On an
+ * "opq" index it first learns the transform on the raw rows (faiss
+ * OPQMatrix::train; skipped when one was injected), then trains the inner
+ * index on the transformed set (faiss IndexPreTransform::train).
+ * Deterministic: same rows and seed give a bitwise-identical transform. */
 int dfann_train(dfann_index *h, int64_t n, const float *x_dev,
                 dfann_stream stream);
 
@@ -103,6 +129,9 @@ int dfann_search(dfann_index *h, int64_t nq, const float *q_dev, int k,
  * R_dev: (nq,k,d) f32 (decoded vectors; zeros at padded slots). On a
  * refine index the rows come from the raw store instead of the code
  * decode: fp32 rows exactly, fp16 rows widened. */
+/* On an "opq" index the rows are dim wide: decoded at opq_dim, then
+ * multiplied by A^T (faiss VectorTransform::reverse_transform of an
+ * orthonormal matrix); with refine they still come from the raw store. */
 int dfann_search_reconstruct(dfann_index *h, int64_t nq, const float *q_dev,
                              int k, float *D_dev, int64_t *I_dev,
                              float *R_dev, dfann_stream stream);
@@ -160,11 +189,12 @@ int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
 int64_t dfann_ntotal(dfann_index *h);             /* faiss .ntotal */
 int dfann_nlist(dfann_index *h);                  /* faiss .nlist */
 int dfann_is_trained(dfann_index *h);
-int dfann_dim(dfann_index *h);
+int dfann_dim(dfann_index *h); /* the caller-facing dim (d_in under opq) */
 /* spec json the index was created with (valid until destroy) */
 const char *dfann_spec_json(dfann_index *h);
 
-/* Coarse centroids to host, (nlist,d) f32. Replaces
+/* Coarse centroids to host, (nlist,d) f32 ((nlist, opq_dim) on an "opq"
+ * index: what faiss extract_index_ivf(index)->quantizer holds). Replaces
  * quantizer.reconstruct_n(0, nlist) at ref index.py:350. Errors on flat
  * (no quantizer — the reference would AttributeError). */
 int dfann_get_centroids(dfann_index *h, float *out_host);
@@ -176,9 +206,26 @@ int dfann_load(const char *path, dfann_index **out);
 
 /* --- trained-artifact exchange (parity-test plumbing: train once, load
  *     the same artifacts into oracle and engine — SURVEY.md §8c) ------- */
+/* On an "opq" index the artifacts are at opq_dim and the call errors until
+ * a transform is set (dfann_set_transform). */
 int dfann_set_trained(dfann_index *h, const float *centroids_host,
                       const float *codebooks_host, const float *vmin_host,
                       const float *vdiff_host);
+/* OPQ transform exchange. A_host: (opq_dim, dim) fp32 row-major.
+ * dfann_get_transform replaces reading faiss LinearTransform::A of
+ * IndexPreTransform::chain[0]; dfann_set_transform replaces assigning it
+ * (with is_trained = true) — it is refused once vectors were added. Both
+ * error on an index without "opq"; get also before a transform exists. */
+int dfann_get_transform(dfann_index *h, float *A_host);
+int dfann_set_transform(dfann_index *h, const float *A_host);
+/* Mirrors faiss VectorTransform::apply: y_dev (n, opq_dim) = x_dev (n, dim)
+ * through the transform — the same kernel dfann_add and every search entry
+ * run, so a row's result is bitwise what the index saw. */
+int dfann_apply_transform(dfann_index *h, int64_t n, const float *x_dev,
+                          float *y_dev, dfann_stream stream);
+/* Mirrors faiss IndexPreTransform::chain / VectorTransform::{d_in, d_out}:
+ * out = {opq on 0|1, d_in, d_out}; d_in == d_out == dim without "opq". */
+int dfann_transform_info(dfann_index *h, int64_t out[3]);
 /* codebooks: (m, 1 << nbits, dsub) fp32 — (m,256,dsub) at nbits=8,
  * (m,16,dsub) at nbits=4 — for dfann_set_trained and dfann_get_codebooks */
 int dfann_get_codebooks(dfann_index *h, float *out_host);
