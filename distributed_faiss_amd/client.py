@@ -300,6 +300,53 @@ class IndexClient:
         results = self.pool.imap(one, self.sub_indexes)
         return self._aggregate_results(results, top_k, q_size, maximize_metric, False)
 
+    def range_search(
+        self, query: np.ndarray, radius: float, index_id: str,
+        filter_pos=None, filter_value=None
+    ) -> Tuple[np.ndarray, np.ndarray, List[object]]:
+        """faiss Index.range_search over all shards: every row of the probed
+        lists with squared l2 distance < radius, or dot product > radius
+        (both strict), optionally among the rows the search_filtered
+        predicate keeps. Returns (lims, scores, meta): query i owns
+        scores/meta[lims[i]:lims[i+1]]; inside a query the shards' results
+        follow each other in shard order, each in its own order (probe
+        slot, then arrival id) — not sorted by distance.
+
+        Dot scores are the TRUE dot products, NOT negated: the negation of
+        search() (quirk 2) is a kept behaviour of the reference, and this
+        method has no reference behaviour to keep.
+
+        Dist mode (one rank per shard) gathers each rank's (lims, scores,
+        meta) with all_gather_object, a host path."""
+        if self.dist_mode:
+            from .dist import all_gather_object
+
+            lims, scores, _ids, meta = self.sub_indexes[0].range_search(
+                index_id, query, radius, filter_pos, filter_value)
+            parts = all_gather_object(
+                (np.asarray(lims), np.asarray(scores), list(meta)))
+        else:
+            def one(idx):
+                lims, scores, _ids, meta = idx.range_search(
+                    index_id, query, radius, filter_pos, filter_value)
+                return np.asarray(lims), np.asarray(scores), list(meta)
+
+            parts = list(self.pool.imap(one, self.sub_indexes))
+        nq = query.shape[0]
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        for pl, _s, _m in parts:
+            lims[1:] += pl[1:]
+        scores = np.empty(lims[nq], dtype=np.float32)
+        meta: List[object] = [None] * int(lims[nq])
+        for i in range(nq):
+            o = int(lims[i])
+            for pl, ps, pm in parts:
+                a, b = int(pl[i]), int(pl[i + 1])
+                scores[o:o + b - a] = ps[a:b]
+                meta[o:o + b - a] = pm[a:b]
+                o += b - a
+        return lims, scores, meta
+
     def _dist_search(self, query, topk, index_id, maximize_metric,
                      return_embeddings, local_search=None):
         """One-rank-per-shard fan-out: local search -> all-gather of

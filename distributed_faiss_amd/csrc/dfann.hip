@@ -349,6 +349,10 @@ struct dfann_index {
   DevBuf cent_bf16;
   DevBuf term2, term3_ws, qn_ws;  // PQ-L2 precomputed tables
   DevBuf pq_lut_ws;  // HBM ADC LUTs for the GLUT scan path
+  // range search: results live here until the next range
+  // call; range_ws = [wave counts | offsets | per-query totals | error word]
+  int64_t range_max = 1LL << 27;  // spec "range_max_results"
+  DevBuf range_D, range_I, range_ws;
   DevBuf filt_ws;    // filtered search: allow-bitmap in CSR-position space
                      // (rebuilt by k_filter_id2pos on every filtered call)
   // refine stage: raw rows in arrival order (row i = id i),
@@ -922,6 +926,8 @@ static dfann_index *create_from_spec(const std::string &js) {
   h->scan_fan = (int)json_int(js, "scan_fan", 1);
   if (h->scan_fan < 1) h->scan_fan = 1;
   if (h->scan_fan > 16) h->scan_fan = 16;
+  h->range_max = json_int(js, "range_max_results", 1LL << 27);
+  if (h->range_max < 0) throw std::runtime_error("range_max_results must be >= 0");
   if (h->d <= 0) { delete h; throw std::runtime_error("bad dim"); }
   h->d_in = h->d;
   h->opq = json_int(js, "opq", 0) != 0;
@@ -1834,27 +1840,36 @@ typedef void (*scan_kern_t)(ScanArgs);
 struct ScanKernels {
   const char *mode;
   scan_kern_t fn[2][2][2];  // [ip][rk][filt]
+  scan_kern_t range_fn[2][2];  // [ip][filt]
 };
 #define DFANN_SCAN_FNS(NAME, MET, SUFFIX)                                      \
   {{k_scan_##NAME##_##MET##SUFFIX, k_scan_##NAME##_##MET##SUFFIX##_f},         \
    {k_scan_##NAME##_##MET##SUFFIX##_rk, k_scan_##NAME##_##MET##SUFFIX##_rk_f}}
+#define DFANN_SCAN_RFNS(NAME, MET, SUFFIX)                                     \
+  {k_scan_##NAME##_##MET##SUFFIX##_rg, k_scan_##NAME##_##MET##SUFFIX##_rg_f}
 #define DFANN_SCAN_ROW(MODE, NAME, SUFFIX, ...)                                \
-  {#MODE, {DFANN_SCAN_FNS(NAME, l2, SUFFIX), DFANN_SCAN_FNS(NAME, ip, SUFFIX)}},
+  {#MODE,                                                                      \
+   {DFANN_SCAN_FNS(NAME, l2, SUFFIX), DFANN_SCAN_FNS(NAME, ip, SUFFIX)},       \
+   {DFANN_SCAN_RFNS(NAME, l2, SUFFIX), DFANN_SCAN_RFNS(NAME, ip, SUFFIX)}},
 #define DFANN_SCAN_ROW_L2(MODE, NAME, SUFFIX, ...)                             \
-  {#MODE, {DFANN_SCAN_FNS(NAME, l2, SUFFIX), {}}},
+  {#MODE, {DFANN_SCAN_FNS(NAME, l2, SUFFIX), {}},                              \
+   {DFANN_SCAN_RFNS(NAME, l2, SUFFIX), {}}},
 static const ScanKernels SCAN_KERNELS[] = {
     DFANN_SCAN_MODES(DFANN_SCAN_ROW, DFANN_SCAN_ROW_L2)};
 #undef DFANN_SCAN_ROW_L2
 #undef DFANN_SCAN_ROW
+#undef DFANN_SCAN_RFNS
 #undef DFANN_SCAN_FNS
 
-static scan_kern_t scan_kernel(ScanMode mode, bool ip, bool rk, bool filt) {
+static scan_kern_t scan_kernel(ScanMode mode, bool ip, bool rk, bool filt,
+                               bool range = false) {
   const ScanKernels &row = SCAN_KERNELS[mode];
-  scan_kern_t fn = row.fn[ip][rk][filt];
+  scan_kern_t fn = range ? row.range_fn[ip][filt] : row.fn[ip][rk][filt];
   if (!fn)
     throw std::runtime_error(std::string("no scan kernel for mode ") +
                              row.mode + (ip ? " ip" : " l2") +
-                             (rk ? " rk" : "") + (filt ? " filtered" : ""));
+                             (range ? " range" : rk ? " rk" : "") +
+                             (filt ? " filtered" : ""));
   return fn;
 }
 
@@ -1868,9 +1883,12 @@ struct ScanPlan {
   int64_t glut_qch;  // GLUT: queries per LUT chunk (not clamped to nq)
 };
 
-static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe) {
+// range: the range kernels — no selector LDS, never a
+// list fan, block size by the register path's rule (k is ignored)
+static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe,
+                          bool range = false) {
   ScanPlan p;
-  bool rk = use_regsel(k);
+  bool rk = range || use_regsel(k);
   switch (h->type) {
     case T_IVFPQ:
       if (h->nbits == 4) {
@@ -1936,11 +1954,12 @@ static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe) {
   // segment fan (spec "scan_fan"): kept as an experiment knob — measured
   // NEGATIVE at the 10M SQ8 shape (per-block staging/extraction overhead
   // outweighs tail imbalance: 1936 -> 1339 GB/s at fan 8), so default 1.
-  p.fan = h->type != T_IVFPQ ? h->scan_fan : 1;
+  p.fan = (h->type != T_IVFPQ && !range) ? h->scan_fan : 1;
   // REGSEL extract scratch aliases the fam region (used only after the
   // scan, behind a barrier) -> max, not sum (kernels.hip ivf_scan_body)
-  p.lds = rk ? std::max((size_t)p.fam_floats * 4, (size_t)REGSEL_LDS_BYTES)
-             : (size_t)p.fam_floats * 4 + SEL_LDS_BYTES;
+  p.lds = range ? (size_t)p.fam_floats * 4
+          : rk  ? std::max((size_t)p.fam_floats * 4, (size_t)REGSEL_LDS_BYTES)
+                : (size_t)p.fam_floats * 4 + SEL_LDS_BYTES;
   if (p.lds > 160 * 1024)
     throw std::runtime_error("scan LDS over budget (m too large)");
   // big-LDS blocks (m=64 LUTs: ~69 KB -> 2 blocks/CU) run 512 threads so
@@ -1965,25 +1984,35 @@ static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe) {
   if (rk && h->type == T_IVFSQ && p.lds <= 4 * 1024) p.scan_bs = 64;
   if (const char *e = getenv("DFANN_SCAN_BS"))  // experiment override
     if (int v = atoi(e)) p.scan_bs = (unsigned)((v / 64) * 64);
+  // the range counts workspace holds 8 waves per (query, probe)
+  if (range) p.scan_bs = std::min(std::max(p.scan_bs, 64u), 512u);
   return p;
 }
 
+struct ScanJob {
+  ScanPlan p;
+  scan_kern_t kern;
+  ScanArgs a;   // everything but the per-chunk pointers
+  int64_t qch;  // queries per launch (nq, or the GLUT chunk)
+};
+
+// Plan, kernel and the arguments that do not change between launches; the
+// filter translate and the PRE per-batch tables run here.
 // allow != nullptr: filtered search. The caller's id-space bitmap is
 // translated to CSR-position space (k_filter_id2pos, on every call — a
 // cache keyed on the caller's pointer would go stale silently) and the
 // FILT twins of the scans test one bit per row. Needs a finalized CSR.
-static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
-                           int nprobe, const int32_t *probes,
-                           const float *keys, int k, float *D, int64_t *I,
-                           hipStream_t stream,
-                           const uint32_t *allow = nullptr) {
+static ScanJob scan_prepare(dfann_index *h, int64_t nq, const float *q,
+                            int nprobe, int k, hipStream_t stream,
+                            const uint32_t *allow, bool range) {
   const bool filt = allow != nullptr;
   const bool ip = h->metric == M_IP;
-  const ScanPlan p = plan_scan(h, k, nprobe);
-  const scan_kern_t kern = scan_kernel(p.mode, ip, use_regsel(k), filt);
+  ScanJob j;
+  j.p = plan_scan(h, k, nprobe, range);
+  const ScanPlan &p = j.p;
+  j.kern = scan_kernel(p.mode, ip, use_regsel(k), filt, range);
   const bool use_pre = p.mode == SCAN_PQ_PRE;
   const bool use_glut = p.mode == SCAN_PQ_G || p.mode == SCAN_PQ_GH;
-  const int fan = p.fan;
 
   ScanArgs a = {};
   a.cent = h->centroids.as<float>();
@@ -1999,7 +2028,7 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   a.stride = h->stride;
   a.rlog = h->csr_arena.rlog;
   a.fam_floats = p.fam_floats;
-  a.fan = fan;
+  a.fan = p.fan;
   if (filt) {
     // outside the scan timing events: not counted in scan_ms
     int64_t waves = (h->ntotal + 63) / 64;
@@ -2009,10 +2038,6 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                        (long long)h->ntotal, h->filt_ws.as<unsigned>());
     a.posbits = h->filt_ws.as<unsigned>();
   }
-  h->ws3.ensure((size_t)nq * nprobe * fan * k * 4);
-  h->ws4.ensure((size_t)nq * nprobe * fan * k * 4);
-  float *cand_d = h->ws3.as<float>();
-  unsigned *cand_p = h->ws4.as<unsigned>();
   if (use_pre) {
     // per-batch tables: q norms + term3 (counted as LUT-build time)
     TimingEv el;
@@ -2030,21 +2055,36 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   }
   // one launch covers all queries, except on the GLUT path, which walks
   // them in chunks of the LUT buffer: build the chunk's LUTs, scan it
-  int64_t qch = use_glut ? std::min(p.glut_qch, nq) : nq;
+  j.qch = use_glut ? std::min(p.glut_qch, nq) : nq;
   if (use_glut) {
-    h->pq_lut_ws.ensure((size_t)qch * nprobe * h->m * 256 *
+    h->pq_lut_ws.ensure((size_t)j.qch * nprobe * h->m * 256 *
                         (p.lut_f16 ? 2 : 4));
     a.glut = h->pq_lut_ws.as<float>();
   }
-  for (int64_t q0 = 0; q0 < nq; q0 += qch) {
-    int64_t nqc = std::min<int64_t>(qch, nq - q0);
+  j.a = a;
+  return j;
+}
+
+// The one scan launch. per_chunk(a, q0) sets the output pointers of the
+// launch that starts at query q0. build_lut = false skips the GLUT build
+// (the buffer still holds the tables of the only chunk).
+template <typename PerChunk>
+static void scan_launch(dfann_index *h, const ScanJob &j, int64_t nq,
+                        const float *q, int nprobe, const int32_t *probes,
+                        const float *keys, hipStream_t stream, bool build_lut,
+                        PerChunk per_chunk) {
+  const ScanPlan &p = j.p;
+  const bool ip = h->metric == M_IP;
+  const bool use_glut = p.mode == SCAN_PQ_G || p.mode == SCAN_PQ_GH;
+  ScanArgs a = j.a;
+  for (int64_t q0 = 0; q0 < nq; q0 += j.qch) {
+    int64_t nqc = std::min<int64_t>(j.qch, nq - q0);
     a.q = q + q0 * h->d;
     a.probes = probes + q0 * nprobe;
     a.keys = keys + q0 * nprobe;
     a.nq = (int)nqc;
-    a.cand_d = cand_d + q0 * nprobe * fan * k;
-    a.cand_p = cand_p + q0 * nprobe * fan * k;
-    if (use_glut) {
+    per_chunk(a, q0);
+    if (use_glut && build_lut) {
       long long qpn = (long long)nqc * nprobe;
       dim3 lg((unsigned)((qpn + PQ_LUT_QPT - 1) / PQ_LUT_QPT),
               (unsigned)h->m);
@@ -2067,25 +2107,163 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
     if (h->timing) e = h->ev_begin(stream);
     // (uploads the slab table after a CSR rebuild: inside the scan events)
     a.codes = h->csr_arena.dev_table(stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nqc * nprobe * fan)),
+    hipLaunchKernelGGL(j.kern, dim3((unsigned)(nqc * nprobe * p.fan)),
                        dim3(p.scan_bs), p.lds, stream, a);
     if (h->timing) h->ev_end(e, stream, h->ev_scan);
   }
-  if (h->timing) {
-    // algorithmic units: sum of probed list lengths
-    std::vector<int32_t> hp((size_t)nq * nprobe);
-    HIP_CHECK(hipMemcpy(hp.data(), probes, hp.size() * 4, hipMemcpyDeviceToHost));
-    int64_t rows = 0;
-    for (int32_t L : hp) rows += h->h_off[L + 1] - h->h_off[L];
-    h->scan_rows += rows;
-    h->scan_bytes += rows * h->stride;
-  }
+}
+
+// timing: algorithmic units of one scan pass, sum of probed list lengths
+static void scan_account(dfann_index *h, int64_t nq, int nprobe,
+                         const int32_t *probes) {
+  if (!h->timing) return;
+  std::vector<int32_t> hp((size_t)nq * nprobe);
+  HIP_CHECK(hipMemcpy(hp.data(), probes, hp.size() * 4, hipMemcpyDeviceToHost));
+  int64_t rows = 0;
+  for (int32_t L : hp) rows += h->h_off[L + 1] - h->h_off[L];
+  h->scan_rows += rows;
+  h->scan_bytes += rows * h->stride;
+}
+
+static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
+                           int nprobe, const int32_t *probes,
+                           const float *keys, int k, float *D, int64_t *I,
+                           hipStream_t stream,
+                           const uint32_t *allow = nullptr) {
+  const bool ip = h->metric == M_IP;
+  const ScanJob j = scan_prepare(h, nq, q, nprobe, k, stream, allow, false);
+  const int fan = j.p.fan;
+  h->ws3.ensure((size_t)nq * nprobe * fan * k * 4);
+  h->ws4.ensure((size_t)nq * nprobe * fan * k * 4);
+  float *cand_d = h->ws3.as<float>();
+  unsigned *cand_p = h->ws4.as<unsigned>();
+  scan_launch(h, j, nq, q, nprobe, probes, keys, stream, true,
+              [&](ScanArgs &a, int64_t q0) {
+                a.cand_d = cand_d + q0 * nprobe * fan * k;
+                a.cand_p = cand_p + q0 * nprobe * fan * k;
+              });
+  scan_account(h, nq, nprobe, probes);
   TimingEv em;
   if (h->timing) em = h->ev_begin(stream);
   launch_merge_cand(stream, cand_d, cand_p, nq, nprobe * fan * k, k,
                     h->cr_ids.as<int64_t>(), ip, D, I, true);
   if (h->timing) h->ev_end(em, stream, h->ev_merge);
   HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// range search: count pass, offsets, one sync for the
+// total, fill pass — the scans' range twins, same plan and row arithmetic
+// as the top-k scans.
+// ---------------------------------------------------------------------------
+
+static void range_check(const dfann_index *h, const uint32_t *allow,
+                        int64_t nbits) {
+  if (h->type == T_FLAT)
+    throw std::runtime_error("range search unsupported for flat");
+  if (h->type == T_HNSW)
+    throw std::runtime_error("range search unsupported for hnswsq");
+  if (h->refine)
+    throw std::runtime_error("range search unsupported with refine");
+  if (!h->trained) throw std::runtime_error("range search on untrained index");
+  if (allow && nbits < h->ntotal)
+    throw std::runtime_error(
+        "range search: allow bitmap covers " + std::to_string(nbits) +
+        " ids but the index holds " + std::to_string(h->ntotal));
+}
+
+static void range_scan(dfann_index *h, int64_t nq, const float *q, int nprobe,
+                       const int32_t *probes, const float *keys, float radius,
+                       const uint32_t *allow, int64_t *lims, int64_t *total_out,
+                       hipStream_t stream) {
+  const ScanJob j = scan_prepare(h, nq, q, nprobe, 1, stream, allow, true);
+  const int W = (int)j.p.scan_bs / 64;
+  // workspace: offsets and counts for 8 waves per (query, probe) whatever
+  // the block size, the per-query totals and the error word
+  const size_t nslot = (size_t)nq * nprobe * 8;
+  h->range_ws.ensure(nslot * 8 + (size_t)nq * 8 + 8 + nslot * 4);
+  long long *off = h->range_ws.as<long long>();
+  long long *tot = off + nslot;
+  int *err = reinterpret_cast<int *>(tot + nq);
+  int *cnt = err + 2;
+  HIP_CHECK(hipMemsetAsync(err, 0, 8, stream));
+  auto pass = [&](int fill) {
+    // a single GLUT chunk's tables survive from the count pass
+    scan_launch(h, j, nq, q, nprobe, probes, keys, stream,
+                fill == 0 || j.qch < nq, [&](ScanArgs &a, int64_t q0) {
+                  a.radius = radius;
+                  a.range_fill = fill;
+                  a.range_cnt = cnt + q0 * nprobe * W;
+                  a.range_off = off + q0 * nprobe * W;
+                  a.range_lims = lims + q0;
+                  a.cr_ids = h->cr_ids.as<int64_t>();
+                  a.range_D = h->range_D.as<float>();
+                  a.range_I = h->range_I.as<int64_t>();
+                  a.range_err = err;
+                });
+    scan_account(h, nq, nprobe, probes);
+  };
+  pass(0);
+  hipLaunchKernelGGL(k_range_offsets, dim3((unsigned)nq), dim3(256), 0, stream,
+                     cnt, nprobe * W, off, tot);
+  hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(256), 0, stream, tot,
+                     (long long)nq, reinterpret_cast<long long *>(lims));
+  HIP_CHECK(hipGetLastError());
+  int64_t total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, lims + nq, 8, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  *total_out = total;
+  if (total > h->range_max)
+    throw std::runtime_error(
+        "range search: " + std::to_string(total) +
+        " results exceed range_max_results = " + std::to_string(h->range_max));
+  if (total == 0) return;
+  h->range_D.ensure((size_t)total * 4);
+  h->range_I.ensure((size_t)total * 8);
+  pass(1);
+  // a fill pass that met another hit count than the count pass stored
+  // nothing outside its segment and raised the error word
+  int herr = 0;
+  HIP_CHECK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (herr)
+    throw std::runtime_error("range search: count and fill passes disagree");
+}
+
+// probes_in == nullptr: coarse-select the index's nprobe lists
+static void range_impl(dfann_index *h, int64_t nq, const float *q_dev,
+                       int nprobe, const int32_t *probes_in,
+                       const float *keys_in, float radius,
+                       const uint32_t *allow, int64_t nbits, int64_t *lims,
+                       int64_t *total_out, const float **D_out,
+                       const int64_t **I_out, hipStream_t stream) {
+  range_check(h, allow, nbits);
+  *total_out = 0;
+  if (nq == 0 || h->ntotal == 0) {
+    HIP_CHECK(hipMemsetAsync(lims, 0, (size_t)(nq + 1) * 8, stream));
+  } else {
+    const float *qi = opq_queries(h, nq, q_dev, stream);
+    finalize_csr(h, stream);
+    const int32_t *probes = probes_in;
+    const float *keys = keys_in;
+    if (!probes) {
+      nprobe = std::min(std::min(h->nprobe, h->nlist), 512);
+      DevBuf &pb = h->ws2;
+      pb.ensure((size_t)nq * nprobe * 8);
+      int32_t *pr = pb.as<int32_t>();
+      float *ke = reinterpret_cast<float *>(pb.as<uint8_t>() +
+                                            (size_t)nq * nprobe * 4);
+      coarse_impl(h, nq, qi, nprobe, pr, ke, stream);
+      probes = pr;
+      keys = ke;
+    } else if (nprobe < 1 || nprobe > 512) {
+      throw std::runtime_error("range search: nprobe must be in 1..512");
+    }
+    range_scan(h, nq, qi, nprobe, probes, keys, radius, allow, lims, total_out,
+               stream);
+  }
+  *D_out = h->range_D.as<float>();
+  *I_out = h->range_I.as<int64_t>();
 }
 
 // allow != nullptr: filtered (id-space bitmap; flat ids are positions)
@@ -2361,6 +2539,34 @@ extern "C" int dfann_search_preassigned_filtered(
                        scan_and_merge(h, nq, qi, nprobe, probes_dev,
                                       keys_dev, kb, Db, Ib, s, allow_bits_dev);
                      });
+  API_END
+}
+
+extern "C" int dfann_range_search(dfann_index *h, int64_t nq,
+                                  const float *q_dev, float radius,
+                                  const uint32_t *allow_dev, int64_t nbits,
+                                  int64_t *lims_dev, int64_t *total_out,
+                                  const float **D_dev_out,
+                                  const int64_t **I_dev_out,
+                                  dfann_stream stream) {
+  API_BEGIN
+  range_impl(h, nq, q_dev, 0, nullptr, nullptr, radius, allow_dev, nbits,
+             lims_dev, total_out, D_dev_out, I_dev_out, (hipStream_t)stream);
+  API_END
+}
+
+extern "C" int dfann_range_search_preassigned(
+    dfann_index *h, int64_t nq, const float *q_dev, int nprobe,
+    const int32_t *probes_dev, const float *keys_dev, float radius,
+    const uint32_t *allow_dev, int64_t nbits, int64_t *lims_dev,
+    int64_t *total_out, const float **D_dev_out, const int64_t **I_dev_out,
+    dfann_stream stream) {
+  API_BEGIN
+  if (!probes_dev || !keys_dev)
+    throw std::runtime_error("range search: null probes / keys");
+  range_impl(h, nq, q_dev, nprobe, probes_dev, keys_dev, radius, allow_dev,
+             nbits, lims_dev, total_out, D_dev_out, I_dev_out,
+             (hipStream_t)stream);
   API_END
 }
 

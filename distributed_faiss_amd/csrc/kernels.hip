@@ -1314,8 +1314,46 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
   return acc;
 }
 
+// Range selector: every row whose distance passes the
+// radius test, in ascending CSR position. A wave owns a contiguous run of
+// rows and its lanes hold them in ascending order, so a hit's rank is the
+// wave's running count plus the hits in the lanes below it (ballot +
+// masked popcount): no LDS, no atomics, no barrier. Pass 0 counts, pass 1
+// writes (value, id) at the offset the exclusive scan of the counts gave.
+struct RangeSel {
+  float radius;
+  int fill;            // 0 = count pass, 1 = fill pass (wave-uniform)
+  const int64_t *ids;  // cr_ids
+  float *D;
+  int64_t *I;
+  int *err;            // count / fill disagreement
+  long long run, end;  // next output slot; end of this wave's segment
+};
+
+// Called by all 64 lanes of a wave together. `val` is the faiss-convention
+// value (L2 distance, un-negated dot product).
+template <bool IS_IP>
+__device__ __forceinline__ void range_offer(RangeSel &r, bool valid, float val,
+                                            long long pos) {
+  bool hit = valid && (IS_IP ? val > r.radius : val < r.radius);
+  unsigned long long b = __ballot(hit);
+  if (r.fill && hit) {
+    long long slot =
+        r.run + __builtin_amdgcn_mbcnt_hi(
+                    (unsigned)(b >> 32),
+                    __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+    if (slot < r.end) {
+      r.D[slot] = val;
+      r.I[slot] = r.ids[pos];
+    } else {
+      *r.err = 1;  // never store outside the counted segment
+    }
+  }
+  r.run += __popcll(b);
+}
+
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
-          bool N4, bool FILT>
+          bool N4, bool FILT, bool RANGE>
 __device__ void ivf_scan_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
@@ -1326,7 +1364,15 @@ __device__ void ivf_scan_body(
     unsigned *__restrict__ cand_p, int fam_floats,
     const float *__restrict__ term2, const float *__restrict__ term3,
     const float *__restrict__ qn, int fan, const float *__restrict__ glut,
-    const unsigned *__restrict__ posbits) {
+    const unsigned *__restrict__ posbits, float radius, int range_fill,
+    int *__restrict__ range_cnt, const long long *__restrict__ range_off,
+    const int64_t *__restrict__ range_lims, const int64_t *__restrict__ cr_ids,
+    float *__restrict__ range_D, int64_t *__restrict__ range_I,
+    int *__restrict__ range_err) {
+  // RANGE: the selector is a RangeSel. The block's rows are split into one
+  // contiguous run per wave (row -> lane mapping inside a wave is the
+  // top-k scans' with a 64-thread "block"), the counts / offsets are per
+  // (query, probe, wave), and the kernel ends after the scan loop.
   // FILT: posbits is the allow-bitmap in CSR-POSITION space (built per
   // call by k_filter_id2pos); a row whose bit is clear is never offered
   // to the selector. The word load is issued next to the row's code load
@@ -1355,6 +1401,15 @@ __device__ void ivf_scan_body(
   long long len = l1 - l0;
   long long s0 = l0 + len * seg / fan;
   long long s1 = l0 + len * (seg + 1) / fan;
+  // (query, probe, wave) slot of the range counts / offsets
+  long long ridx = 0;
+  if (RANGE)
+    ridx = ((long long)bq * nprobe + bp) * (blockDim.x >> 6) +
+           (threadIdx.x >> 6);
+  if (RANGE && s0 == s1) {
+    if (!range_fill && (threadIdx.x & 63) == 0) range_cnt[ridx] = 0;
+    return;
+  }
   if (s0 == s1) {
     for (int j = threadIdx.x; j < k; j += blockDim.x) {
       cand_d[out_base + j] = DFANN_FLT_MAX;
@@ -1481,7 +1536,33 @@ __device__ void ivf_scan_body(
 
   RegTopK<16> loc;
   Sel s;
-  if (REGSEL) {
+  RangeSel rs;
+  // Rows [SCAN_R0, SCAN_R1) are shared by SCAN_NT threads, this one being
+  // SCAN_TID: the block's segment, or in range mode the wave's part of it.
+  // (Macros, so that the top-k kernels see the expressions they always had
+  // and compile to what they compiled to before range mode existed.)
+  long long rw0 = 0, rw1 = 0;
+#define SCAN_R0 (RANGE ? rw0 : s0)
+#define SCAN_R1 (RANGE ? rw1 : s1)
+#define SCAN_NT (RANGE ? 64u : blockDim.x)
+#define SCAN_TID (RANGE ? (threadIdx.x & 63u) : threadIdx.x)
+  if (RANGE) {
+    const int W = blockDim.x >> 6, w = threadIdx.x >> 6;
+    rw0 = s0 + len * w / W;
+    rw1 = s0 + len * (w + 1) / W;
+    rs.radius = radius;
+    rs.fill = range_fill;
+    rs.ids = cr_ids;
+    rs.D = range_D;
+    rs.I = range_I;
+    rs.err = range_err;
+    rs.run = 0;
+    rs.end = 0;
+    if (range_fill) {
+      rs.run = range_lims[bq] + range_off[ridx];
+      rs.end = rs.run + range_cnt[ridx];
+    }
+  } else if (REGSEL) {
     loc.init();
   } else {
     s = sel_carve(selbase);
@@ -1492,14 +1573,14 @@ __device__ void ivf_scan_body(
   // --- scan ---
   if (FAM == 1) {
     // 16-lane-per-vector tree reduction (tolerance parity path)
-    int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const int NG16 = blockDim.x >> 4;  // row groups per block
-    for (long long base = s0; base < s1; base += (long long)NG16 * 8) {
+    int sub = threadIdx.x & 15, grp = SCAN_TID >> 4;
+    const int NG16 = SCAN_NT >> 4;  // row groups per block (RANGE: wave)
+    for (long long base = SCAN_R0; base < SCAN_R1; base += (long long)NG16 * 8) {
       if (!REGSEL) sel_guard(s, k, NG16 * 8);
       for (int u = 0; u < 8; ++u) {
         long long pos = base + (long long)u * NG16 + grp;
         float dist = 0.f;
-        bool valid = pos < s1;
+        bool valid = pos < SCAN_R1;
         bool allow = true;
         if (FILT && valid) allow = pos_allowed(posbits, pos);
         if (valid) {
@@ -1517,7 +1598,10 @@ __device__ void ivf_scan_body(
           for (int o = 8; o > 0; o >>= 1) part += __shfl_xor(part, o, 16);
           dist = IS_IP ? -part : part;
         }
-        if (valid && allow && sub == 0) {
+        if (RANGE) {
+          range_offer<IS_IP>(rs, valid && allow && sub == 0,
+                             IS_IP ? -dist : dist, pos);
+        } else if (valid && allow && sub == 0) {
           if (REGSEL) loc.push(dist, (unsigned)pos);
           else sel_try(s, dist, (unsigned)pos);
         }
@@ -1531,12 +1615,12 @@ __device__ void ivf_scan_body(
     // all lanes converge to the same bitwise sum.
     {
       const float *ubuf = fam, *vbuf = fam + d;
-      int g8 = threadIdx.x & 7, grp = threadIdx.x >> 3;  // 32 row-groups
+      int g8 = threadIdx.x & 7, grp = SCAN_TID >> 3;  // 32 row-groups
       const bool onechunk = d <= 128;  // lane covers one 16-B chunk
-      const int NG8 = blockDim.x >> 3;  // row groups per block
+      const int NG8 = SCAN_NT >> 3;  // row groups per block (RANGE: wave)
       // row sets per iteration (8 measured 1.9 -> 1.1 TB/s)
       constexpr int UR = 4;
-      for (long long base = s0; base < s1; base += (long long)NG8 * UR) {
+      for (long long base = SCAN_R0; base < SCAN_R1; base += (long long)NG8 * UR) {
         if (!REGSEL) sel_guard(s, k, NG8 * UR);
         if (onechunk) {
           // issue all UR row-set loads up front: UR independent HBM
@@ -1547,7 +1631,7 @@ __device__ void ivf_scan_body(
 #pragma unroll
           for (int u = 0; u < UR; ++u) {
             long long pos = base + (long long)u * NG8 + grp;
-            val4[u] = pos < s1;
+            val4[u] = pos < SCAN_R1;
             ok4[u] = val4[u];
             if (FILT && val4[u]) ok4[u] = pos_allowed(posbits, pos);
             int t0 = g8 * 16;
@@ -1584,7 +1668,10 @@ __device__ void ivf_scan_body(
             part += __shfl_xor(part, 2, 8);
             part += __shfl_xor(part, 1, 8);
             float dist = IS_IP ? -(bias + part) : part;
-            if (ok4[u] && g8 == 0) {
+            if (RANGE) {
+              range_offer<IS_IP>(rs, ok4[u] && g8 == 0, IS_IP ? -dist : dist,
+                                 pos);
+            } else if (ok4[u] && g8 == 0) {
               if (REGSEL) loc.push(dist, (unsigned)pos);
               else sel_try(s, dist, (unsigned)pos);
             }
@@ -1593,7 +1680,7 @@ __device__ void ivf_scan_body(
 #pragma unroll
           for (int u = 0; u < UR; ++u) {
             long long pos = base + (long long)u * NG8 + grp;
-            bool valid = pos < s1;
+            bool valid = pos < SCAN_R1;
             bool allow = true;
             if (FILT && valid) allow = pos_allowed(posbits, pos);
             float part = 0.f;
@@ -1623,7 +1710,10 @@ __device__ void ivf_scan_body(
             part += __shfl_xor(part, 2, 8);
             part += __shfl_xor(part, 1, 8);
             float dist = IS_IP ? -(bias + part) : part;
-            if (valid && allow && g8 == 0) {
+            if (RANGE) {
+              range_offer<IS_IP>(rs, valid && allow && g8 == 0,
+                                 IS_IP ? -dist : dist, pos);
+            } else if (valid && allow && g8 == 0) {
               if (REGSEL) loc.push(dist, (unsigned)pos);
               else sel_try(s, dist, (unsigned)pos);
             }
@@ -1641,20 +1731,24 @@ __device__ void ivf_scan_body(
     // load batches cost 183 VGPRs (2 waves/SIMD); 2 rows are 90 (5 waves)
     // and measured 1.7-2.6x the scan rate (BASELINE.md "4-bit PQ").
     const int UROWS = (FAM == 0 && !N4) ? 4 : 2;
-    const int BS = blockDim.x;
-    for (long long base = s0; base < s1; base += (long long)UROWS * BS) {
+    const int BS = SCAN_NT;
+    for (long long base = SCAN_R0; base < SCAN_R1; base += (long long)UROWS * BS) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (u >= UROWS) break;
-        long long pos = base + (long long)u * BS + threadIdx.x;
-        if (pos < s1) {
+        long long pos = base + (long long)u * BS + SCAN_TID;
+        bool hit = false;  // RANGE: valid and allowed
+        float dist = 0.f;
+        if (pos < SCAN_R1) {
           bool allow = true;
           if (FILT) allow = pos_allowed(posbits, pos);
           const uint8_t *cp = slab_row(codes, rlog, pos, stride);
           float acc = scan_row_dist<FAM, IS_IP, L16, N4>(cp, fam, d, m);
-          float dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
-          if (allow) loc.push(dist, (unsigned)pos);
+          dist = IS_IP ? -(bias + acc) : (PRE ? bias + acc : acc);
+          if (RANGE) hit = allow;
+          else if (allow) loc.push(dist, (unsigned)pos);
         }
+        if (RANGE) range_offer<IS_IP>(rs, hit, IS_IP ? -dist : dist, pos);
       }
     }
   } else {
@@ -1675,6 +1769,19 @@ __device__ void ivf_scan_body(
       }
     }
   }
+  if (RANGE) {
+    // count pass: the wave's total. Fill pass: it must have written
+    // exactly the counted segment.
+    if ((threadIdx.x & 63) == 0) {
+      if (!range_fill) range_cnt[ridx] = (int)rs.run;
+      else if (rs.run != rs.end) *range_err = 1;
+    }
+    return;
+  }
+#undef SCAN_R0
+#undef SCAN_R1
+#undef SCAN_NT
+#undef SCAN_TID
   __syncthreads();
   if (REGSEL) {
     regtopk_block_extract<16>(loc, k, selbase, cand_d + out_base,
@@ -1711,6 +1818,9 @@ __device__ void ivf_scan_body(
 //   GLUT: LUT staged from HBM (built by k_pq_lut) instead of computed in
 //         the scan prologue; L16: those rows are __half (pq_lut_f16)
 //   N4:   4-bit PQ (nbits=4), in-kernel fp32 LUT only
+// _rg[_f]: range mode (RANGE=true). One kernel serves the
+// count and the fill pass (a.range_fill); it has the register path's row
+// loop (REGSEL=true) but no top-k state and no LDS beyond the fam region.
 // ---------------------------------------------------------------------------
 struct ScanArgs {
   const float *q, *cent, *cb, *sq_vmin, *sq_scale;
@@ -1726,18 +1836,32 @@ struct ScanArgs {
   int fan;                          // base modes (not PRE / GLUT)
   const float *glut;                // GLUT
   const unsigned *posbits;          // _f
+  // _rg (range mode)
+  float radius;
+  int range_fill;             // 0 = count pass, 1 = fill pass
+  int *range_cnt;             // (nq, nprobe, W) hits per wave, W = block / 64
+  const long long *range_off; // exclusive scan of range_cnt inside a query
+  const int64_t *range_lims;  // (nq + 1) first output slot per query
+  const int64_t *cr_ids;
+  float *range_D;
+  int64_t *range_I;
+  int *range_err;
 };
 
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
-          bool N4, bool FILT>
+          bool N4, bool FILT, bool RANGE>
 __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
-  ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT>(
+  ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE>(
       a.q, a.cent, a.cb, a.sq_vmin, a.sq_scale, a.probes, a.keys, a.codes,
       a.off, a.nq, a.nprobe, a.d, a.m, a.dsub, a.k, a.stride, a.rlog,
       a.cand_d, a.cand_p, a.fam_floats, PRE ? a.term2 : nullptr,
       PRE ? a.term3 : nullptr, PRE ? a.qn : nullptr,
-      (PRE || GLUT) ? 1 : a.fan, GLUT ? a.glut : nullptr,
-      FILT ? a.posbits : nullptr);
+      (PRE || GLUT || RANGE) ? 1 : a.fan, GLUT ? a.glut : nullptr,
+      FILT ? a.posbits : nullptr, RANGE ? a.radius : 0.f,
+      RANGE ? a.range_fill : 0, RANGE ? a.range_cnt : nullptr,
+      RANGE ? a.range_off : nullptr, RANGE ? a.range_lims : nullptr,
+      RANGE ? a.cr_ids : nullptr, RANGE ? a.range_D : nullptr,
+      RANGE ? a.range_I : nullptr, RANGE ? a.range_err : nullptr);
 }
 
 //  (MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)
@@ -1751,19 +1875,24 @@ __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
   X(SQ8, sq8, , 2, false, false, false, false)                                 \
   X(SQF, sqf, , 3, false, false, false, false)       /* SQ fp16 */
 
-#define DFANN_SCAN_KERNEL(KNAME, FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT) \
+#define DFANN_SCAN_KERNEL(KNAME, FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, \
+                          RANGE)                                               \
   extern "C" __global__ __launch_bounds__(512) void KNAME(ScanArgs a) {        \
-    scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT>(a);               \
+    scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE>(a);        \
   }
 #define DFANN_SCAN_METRIC(NAME, MET, SUFFIX, FAM, IS_IP, PRE, GLUT, L16, N4)   \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX, FAM, IS_IP, false, PRE,     \
-                    GLUT, L16, N4, false)                                      \
+                    GLUT, L16, N4, false, false)                               \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_f, FAM, IS_IP, false, PRE, \
-                    GLUT, L16, N4, true)                                       \
+                    GLUT, L16, N4, true, false)                                \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk, FAM, IS_IP, true, PRE, \
-                    GLUT, L16, N4, false)                                      \
+                    GLUT, L16, N4, false, false)                               \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk_f, FAM, IS_IP, true,    \
-                    PRE, GLUT, L16, N4, true)
+                    PRE, GLUT, L16, N4, true, false)                           \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rg, FAM, IS_IP, true, PRE, \
+                    GLUT, L16, N4, false, true)                                \
+  DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rg_f, FAM, IS_IP, true,    \
+                    PRE, GLUT, L16, N4, true, true)
 #define DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)         \
   DFANN_SCAN_METRIC(NAME, l2, SUFFIX, FAM, false, PRE, GLUT, L16, N4)
 #define DFANN_SCAN_DEF(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)            \
@@ -1774,6 +1903,50 @@ DFANN_SCAN_MODES(DFANN_SCAN_DEF, DFANN_SCAN_DEF_L2)
 #undef DFANN_SCAN_DEF_L2
 #undef DFANN_SCAN_METRIC
 #undef DFANN_SCAN_KERNEL
+
+// Range search offsets: fixed-order integer exclusive scans.
+// block_excl_scan: out[i] = sum(in[0 .. i-1]) for i < n, returns the total
+// to every thread. 256 threads, each owning a contiguous chunk.
+template <typename TIn>
+__device__ long long block_excl_scan(const TIn *__restrict__ in, long long n,
+                                     long long *__restrict__ out) {
+  __shared__ long long part[256];
+  long long per = (n + 255) / 256;
+  long long i0 = min((long long)threadIdx.x * per, n);
+  long long i1 = min(i0 + per, n);
+  long long sum = 0;
+  for (long long i = i0; i < i1; ++i) sum += (long long)in[i];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  long long before = 0, total = 0;
+  for (int t = 0; t < 256; ++t) {
+    if (t == (int)threadIdx.x) before = total;
+    total += part[t];
+  }
+  for (long long i = i0; i < i1; ++i) {
+    out[i] = before;
+    before += (long long)in[i];
+  }
+  return total;
+}
+
+// one block per query: its nprobe * W wave counts -> offsets inside the
+// query, and the query's total
+__global__ __launch_bounds__(256) void k_range_offsets(
+    const int *__restrict__ cnt, int n, long long *__restrict__ off,
+    long long *__restrict__ total) {
+  long long qb = (long long)blockIdx.x * n;
+  long long t = block_excl_scan<int>(cnt + qb, n, off + qb);
+  if (threadIdx.x == 0) total[blockIdx.x] = t;
+}
+
+// single block: per-query totals -> lims (nq + 1)
+__global__ __launch_bounds__(256) void k_range_lims(
+    const long long *__restrict__ total, long long nq,
+    long long *__restrict__ lims) {
+  long long t = block_excl_scan<long long>(total, nq, lims);
+  if (threadIdx.x == 0) lims[nq] = t;
+}
 // ---------------------------------------------------------------------------
 // k_pq_lut: ADC lookup tables to HBM, one 256-entry row per (query,
 // probe, subspace) at out[(qp)*m*256 + j*256 + c] — the scan's GLUT

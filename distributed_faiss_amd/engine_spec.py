@@ -217,6 +217,7 @@ ENGINE_PERF_KNOBS = (
     "pq_lut_mb",      # GLUT chunk budget
     "pq_lut_f16",     # fp16 ADC tables (tolerance path)
     "scan_fan",       # list-segment fan (experiment knob)
+    "range_max_results",  # range search: largest result, in hits
 )
 
 

@@ -81,6 +81,13 @@ def load_lib():
     lib.dfann_search_preassigned_filtered.argtypes = [
         c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
         c.c_int, c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.dfann_range_search.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_float, c.c_void_p, c.c_int64,
+        c.c_void_p, P(c.c_int64), P(c.c_void_p), P(c.c_void_p), c.c_void_p]
+    lib.dfann_range_search_preassigned.argtypes = [
+        c.c_void_p, c.c_int64, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p,
+        c.c_float, c.c_void_p, c.c_int64, c.c_void_p, P(c.c_int64),
+        P(c.c_void_p), P(c.c_void_p), c.c_void_p]
     lib.dfann_set_nprobe.argtypes = [c.c_void_p, c.c_int]
     lib.dfann_set_k_factor.argtypes = [c.c_void_p, c.c_float]
     lib.dfann_refine_info.argtypes = [c.c_void_p, c.c_void_p]
@@ -151,6 +158,15 @@ class PackedFilter:
     def __init__(self, bits, nbits):
         self.bits = bits
         self.nbits = int(nbits)
+
+
+class _DevView:
+    """A 1-d engine-owned device array, exposed to torch without a copy."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {
+            "shape": (n,), "typestr": typestr, "data": (ptr, False),
+            "version": 2, "strides": None}
 
 
 class HipEngine:
@@ -360,6 +376,68 @@ class HipEngine:
             ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
             self._stream(torch)))
         return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- range search --------------------------------------
+
+    def range_search(self, q, radius, allow=None):
+        """faiss Index.range_search: every row of the probed lists with
+        L2 dist < radius / IP dot > radius (strict; the values `search`
+        returns, dot products un-negated), optionally under an allow mask
+        (numpy bool array of length >= ntotal, or a PackedFilter).
+        Returns numpy (lims (nq+1) int64, D float32, I int64); query i owns
+        D/I[lims[i]:lims[i+1]], ordered by probe slot, then arrival id."""
+        torch = _torch()
+        qt = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32)).cuda()
+        f = self._packed(allow) if allow is not None else None
+        lims, D, I = self.range_search_dev(
+            qt, radius, f.bits if f else None, f.nbits if f else 0)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    def range_search_dev(self, qt, radius, bits_t=None, nbits=0):
+        """Device-resident range search: torch cuda tensors (lims, D, I),
+        copied out of the engine's result buffers. The call synchronizes
+        the stream (the result size is read back), so it does not capture
+        into a graph."""
+        return self._range(qt, radius, bits_t, nbits, None, None)
+
+    def range_search_preassigned(self, q, probes, keys, radius, allow=None):
+        """faiss IndexIVF.range_search_preassigned over `coarse`'s probes
+        and keys; numpy in and out, as range_search."""
+        torch = _torch()
+        qt = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32)).cuda()
+        pt = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.int32)).cuda()
+        kt = torch.as_tensor(np.ascontiguousarray(keys, dtype=np.float32)).cuda()
+        f = self._packed(allow) if allow is not None else None
+        lims, D, I = self._range(qt, radius, f.bits if f else None,
+                                 f.nbits if f else 0, pt, kt)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    def _range(self, qt, radius, bits_t, nbits, pt, kt):
+        torch = _torch()
+        nq = qt.shape[0]
+        lims = torch.empty(nq + 1, dtype=torch.int64, device="cuda")
+        total = ctypes.c_int64(0)
+        Dp, Ip = ctypes.c_void_p(), ctypes.c_void_p()
+        bits = ctypes.c_void_p(bits_t.data_ptr()) if bits_t is not None else None
+        tail = (ctypes.c_float(radius), bits, int(nbits),
+                ctypes.c_void_p(lims.data_ptr()), ctypes.byref(total),
+                ctypes.byref(Dp), ctypes.byref(Ip), self._stream(torch))
+        if pt is None:
+            _check(self.lib, self.lib.dfann_range_search(
+                self.h, nq, ctypes.c_void_p(qt.data_ptr()), *tail))
+        else:
+            _check(self.lib, self.lib.dfann_range_search_preassigned(
+                self.h, nq, ctypes.c_void_p(qt.data_ptr()), pt.shape[1],
+                ctypes.c_void_p(pt.data_ptr()), ctypes.c_void_p(kt.data_ptr()),
+                *tail))
+        n = int(total.value)
+        if n == 0:
+            return (lims, torch.empty(0, dtype=torch.float32, device="cuda"),
+                    torch.empty(0, dtype=torch.int64, device="cuda"))
+        # the engine's buffers are reused by the next range call: copy out
+        D = torch.as_tensor(_DevView(Dp.value, n, "<f4"), device="cuda").clone()
+        I = torch.as_tensor(_DevView(Ip.value, n, "<i8"), device="cuda").clone()
+        return lims, D, I
 
     # -- introspection / artifacts ----------------------------------------
 

@@ -254,6 +254,45 @@ class Index:
             # rows were added in between: extend the bitmap and retry
         return scores, indexes, self.metadata_for(indexes), None
 
+    def range_search(
+        self, query_batch: np.ndarray, radius: float, filter_pos=None,
+        filter_value=None
+    ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, List[object]]:
+        """faiss Index.range_search: every row of the probed lists closer
+        than `radius` (l2: squared distance < radius; dot: dot product >
+        radius, both strict), optionally among the rows the filter predicate
+        of search_filtered keeps (filter_pos not None). Returns (lims,
+        scores, indexes, meta): query i owns scores/indexes/meta
+        [lims[i]:lims[i+1]], ordered by probe slot, then arrival id — not by
+        distance; `meta` is a flat list aligned with `scores`."""
+        query_batch = np.ascontiguousarray(query_batch, dtype=np.float32)
+        while True:
+            with self.index_lock:
+                if self.state != IndexState.TRAINED:
+                    raise RuntimeError(f"Server index is not trained. state: {self.state}")
+                engine = self.engine
+                if not hasattr(engine, "range_search"):
+                    raise NotImplementedError(
+                        f"engine {type(engine).__name__} has no range_search: "
+                        "range search needs the HIP engine")
+                ntotal = engine.ntotal
+                if filter_pos is None:
+                    lims, scores, indexes = engine.range_search(query_batch, radius)
+                    break
+            # as search_filtered: the bitmap is built outside index_lock
+            flt = self._filter_for(engine, ntotal, filter_pos, filter_value)
+            with self.index_lock:
+                if self.state != IndexState.TRAINED:
+                    raise RuntimeError(f"Server index is not trained. state: {self.state}")
+                if self.engine is engine and engine.ntotal == ntotal:
+                    lims, scores, indexes = engine.range_search(
+                        query_batch, radius, flt)
+                    break
+            # rows were added in between: extend the bitmap and retry
+        with self.buffer_lock:
+            meta = [self.id_to_metadata[i] for i in indexes]
+        return lims, scores, indexes, meta
+
     @staticmethod
     def _filter_allows(m, filter_pos, filter_value) -> bool:
         # the reference predicate, ref client.py:236-240

@@ -166,6 +166,16 @@ class IndexServer:
         return index.search_filtered(query_batch, top_k, filter_pos,
                                      filter_value)
 
+    def range_search(
+        self, index_id: str, query_batch: np.ndarray, radius: float,
+        filter_pos=None, filter_value=None
+    ) -> Tuple:
+        """Range search (Index.range_search): (lims, scores, ids, meta),
+        `meta` flat and aligned with `scores`."""
+        index = self._get_index(index_id)
+        return index.range_search(query_batch, radius, filter_pos,
+                                  filter_value)
+
     def search_ids_dev(self, index_id: str, qt, top_k: int):
         """Device-resident (D, I) search — the distributed client's timed
         serving step (no metadata epilogue, results stay in HBM)."""

@@ -167,6 +167,43 @@ int dfann_search_preassigned_filtered(dfann_index *h, int64_t nq,
         const float *keys_dev, int k, const uint32_t *allow_bits_dev,
         int64_t nbits, float *D_dev, int64_t *I_dev, dfann_stream stream);
 
+/* Range search. Mirrors faiss Index::range_search over an
+ * IVF index: every row of the min(nprobe, nlist, 512) probed lists whose
+ * distance passes the STRICT radius test — L2: dist < radius (squared L2,
+ * the value dfann_search returns); IP: dot > radius (the un-negated dot
+ * product dfann_search returns). Distances are bitwise dfann_search's.
+ * allow_dev: optional allow-bitmap (dfann_search_filtered conventions,
+ * nbits >= ntotal); NULL = unfiltered, nbits ignored.
+ * lims_dev: (nq+1) i64 device, lims[0] = 0; query i owns D/I[lims[i] ..
+ * lims[i+1]). *total_out = lims[nq]. *D_dev_out / *I_dev_out: engine-owned
+ * device arrays of total f32 / i64 arrival ids, valid until the next range
+ * call on the handle or its destruction (NULL while nothing was ever
+ * returned). Order inside a query: probe slot ascending, then ascending
+ * CSR position (= ascending arrival id) inside the list; not by distance.
+ * Byte-identical run to run.
+ * The call synchronizes the stream (once to read the total, once after the
+ * fill pass to read its error word): it cannot be captured into a graph.
+ * Workspace: nq * nprobe * 8 wave counts (4 B) and offsets (8 B).
+ * Spec key "range_max_results" (default 1 << 27 hits, 1.6 GB of D + I): a
+ * larger total is an error naming the key, the total and the limit, raised
+ * before the result arrays grow. radius NaN: empty result.
+ * Errors: flat, hnswsq, an index with refine (faiss IndexRefine has no
+ * range search either), an untrained index, nbits < ntotal. */
+int dfann_range_search(dfann_index *h, int64_t nq, const float *q_dev,
+                       float radius, const uint32_t *allow_dev, int64_t nbits,
+                       int64_t *lims_dev, int64_t *total_out,
+                       const float **D_dev_out, const int64_t **I_dev_out,
+                       dfann_stream stream);
+/* The same over caller-supplied probe lists (dfann_coarse's probes and
+ * keys). Mirrors faiss IndexIVF::range_search_preassigned. A list named
+ * twice contributes its hits twice. 1 <= nprobe <= 512. */
+int dfann_range_search_preassigned(dfann_index *h, int64_t nq,
+        const float *q_dev, int nprobe, const int32_t *probes_dev,
+        const float *keys_dev, float radius, const uint32_t *allow_dev,
+        int64_t nbits, int64_t *lims_dev, int64_t *total_out,
+        const float **D_dev_out, const int64_t **I_dev_out,
+        dfann_stream stream);
+
 /* --- knobs / introspection -------------------------------------------- */
 
 /* ref index.py:352-356. Effective nprobe is min(nprobe, nlist, 512) at
