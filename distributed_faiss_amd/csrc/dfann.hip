@@ -285,6 +285,13 @@ enum { M_IP = 0, M_L2 = 1 };
 
 static int round16(int b) { return (b + 15) & ~15; }
 
+// work items per row of k_sq_encode: one per dimension, or for the packed
+// widths one per owned unit of the row's stride (4-bit: a byte, 6-bit: a
+// 3-byte group), so that pad bytes are written (as zero) too
+static int sq_encode_items(int bits, int d, int stride) {
+  return bits == 4 ? stride : bits == 6 ? (stride + 2) / 3 : d;
+}
+
 struct TimingEv {
   hipEvent_t a, b;
 };
@@ -294,7 +301,11 @@ struct dfann_index {
   int type = T_FLAT;
   int metric = M_IP;
   int d = 0, nlist = 0, m = 0, nbits = 8, dsub = 0, nprobe = 1;
-  bool sq8 = false;  // ivfsq: true = 8bit, false = fp16
+  // ivfsq code width: 16 = fp16, 8 / 6 / 4 = integer codes trained on
+  // per-dimension ranges; hnswsq is always 8
+  int sq_bits = 16;
+  bool sq_int() const { return sq_bits != 16; }
+  float sq_q() const { return (float)((1 << sq_bits) - 1); }  // top code
   uint64_t seed = 1234;
   bool trained = false;
   int64_t ntotal = 0;
@@ -913,7 +924,10 @@ static dfann_index *create_from_spec(const std::string &js) {
   h->nbits = (int)json_int(js, "nbits", 8);
   h->nprobe = (int)json_int(js, "nprobe", 1);
   h->seed = (uint64_t)json_int(js, "seed", 1234);
-  h->sq8 = json_str(js, "sq_type", "fp16") == "8bit";
+  {
+    std::string sq = json_str(js, "sq_type", "fp16");
+    h->sq_bits = sq == "8bit" ? 8 : sq == "6bit" ? 6 : sq == "4bit" ? 4 : 16;
+  }
   h->ws_mb = (int)json_int(js, "ws_mb", 512);
   if (h->ws_mb < 1) h->ws_mb = 1;
   h->coarse_bf16 = json_int(js, "coarse_bf16", 0) != 0;
@@ -988,7 +1002,9 @@ static dfann_index *create_from_spec(const std::string &js) {
       }
     }
   } else if (h->type == T_IVFSQ) {
-    h->code_bytes = h->sq8 ? h->d : 2 * h->d;
+    // integer codes are a packed little-endian bit stream (faiss
+    // Codec4bit / Codec6bit); 8 bits is the byte-per-dim case of it
+    h->code_bytes = h->sq_int() ? (h->d * h->sq_bits + 7) / 8 : 2 * h->d;
   } else if (h->type == T_IVFFLAT) {
     h->code_bytes = 4 * h->d;
   } else if (h->type == T_HNSW) {
@@ -1012,7 +1028,7 @@ static dfann_index *create_from_spec(const std::string &js) {
     h->hnsw_efc = (int)json_int(js, "ef_construction", 100);
     if (h->hnsw_efc < 1) h->hnsw_efc = 1;
     if (h->hnsw_efc > 512) h->hnsw_efc = 512;
-    h->sq8 = true;
+    h->sq_bits = 8;
     h->code_bytes = h->d;
   } else {
     h->code_bytes = 4 * h->d;
@@ -1077,7 +1093,7 @@ static void hnsw_train_ranges(dfann_index *h, int64_t n, const float *x,
   hipLaunchKernelGGL(k_minmax_decode, grid1d(h->d), dim3(256), 0, stream,
                      mn.as<unsigned>(), mx.as<unsigned>(), h->d,
                      h->sq_vmin.as<float>(), h->sq_vdiff.as<float>(),
-                     h->sq_scale.as<float>());
+                     h->sq_scale.as<float>(), h->sq_q());
   HIP_CHECK(hipStreamSynchronize(stream));
 }
 
@@ -1101,7 +1117,7 @@ static void train_impl(dfann_index *h, int64_t n, const float *x,
   rownorms(h->centroids.as<float>(), h->nlist, h->d, h->cnorm.as<float>(),
            stream);
   refresh_cent_bf16(h, stream);  // bf16 image for the assign below
-  if (h->type == T_IVFPQ || (h->type == T_IVFSQ && h->sq8)) {
+  if (h->type == T_IVFPQ || (h->type == T_IVFSQ && h->sq_int())) {
     DevBuf asg, resid;
     asg.ensure((size_t)n * 4);
     resid.ensure((size_t)n * h->d * 4);
@@ -1126,7 +1142,7 @@ static void train_impl(dfann_index *h, int64_t n, const float *x,
                       stream);
         trace_point("train:pq-sub", stream);
       }
-    } else {  // SQ8 ranges on residuals
+    } else {  // SQ8 / SQ6 / SQ4 ranges on residuals
       DevBuf mn, mx;
       mn.ensure((size_t)h->d * 4);
       mx.ensure((size_t)h->d * 4);
@@ -1141,7 +1157,7 @@ static void train_impl(dfann_index *h, int64_t n, const float *x,
       hipLaunchKernelGGL(k_minmax_decode, grid1d(h->d), dim3(256), 0, stream,
                          mn.as<unsigned>(), mx.as<unsigned>(), h->d,
                          h->sq_vmin.as<float>(), h->sq_vdiff.as<float>(),
-                         h->sq_scale.as<float>());
+                         h->sq_scale.as<float>(), h->sq_q());
     }
   }
   refresh_cent_bf16(h, stream);  // + term2 now that codebooks exist
@@ -1306,11 +1322,12 @@ static void encode_chunk(dfann_index *h, int64_t n, const float *x,
                          h->stride, rlog, row0, dst);
     }
   } else {
-    hipLaunchKernelGGL(k_sq_encode, grid1d(n * h->d), dim3(256), 0, stream,
-                       resid.as<float>(),
-                       h->sq8 ? h->sq_vmin.as<float>() : nullptr,
-                       h->sq8 ? h->sq_vdiff.as<float>() : nullptr, n, h->d,
-                       h->stride, h->sq8 ? 0 : 1, rlog, row0, dst);
+    hipLaunchKernelGGL(k_sq_encode,
+                       grid1d(n * sq_encode_items(h->sq_bits, h->d, h->stride)),
+                       dim3(256), 0, stream, resid.as<float>(),
+                       h->sq_int() ? h->sq_vmin.as<float>() : nullptr,
+                       h->sq_int() ? h->sq_vdiff.as<float>() : nullptr, n, h->d,
+                       h->stride, h->sq_bits, rlog, row0, dst);
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -1494,7 +1511,7 @@ static void hnsw_add(dfann_index *h, int64_t n, const float *x,
       int64_t c = std::min(CH, n - s0);
       hipLaunchKernelGGL(k_sq_encode, grid1d(c * h->d), dim3(256), 0, stream,
                          x + s0 * h->d, h->sq_vmin.as<float>(),
-                         h->sq_vdiff.as<float>(), c, h->d, h->stride, 0,
+                         h->sq_vdiff.as<float>(), c, h->d, h->stride, 8,
                          h->csr_arena.rlog, n0 + s0,
                          h->csr_arena.dev_table_mut(stream));
     }
@@ -1904,8 +1921,11 @@ static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe,
       p.fam_floats = h->d;
       break;
     case T_IVFSQ:
-      p.mode = h->sq8 ? SCAN_SQ8 : SCAN_SQF;
-      p.fam_floats = h->sq8 ? 2 * h->d : h->d;
+      p.mode = h->sq_bits == 8   ? SCAN_SQ8
+               : h->sq_bits == 6 ? SCAN_SQ6
+               : h->sq_bits == 4 ? SCAN_SQ4
+                                 : SCAN_SQF;
+      p.fam_floats = h->sq_int() ? 2 * h->d : h->d;
       break;
     default:
       throw std::runtime_error("scan on flat index");
@@ -2609,7 +2629,8 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
   else if (h->type == T_IVFFLAT) rtype = 0;
   else if (h->type == T_IVFPQ) rtype = h->nbits == 4 ? 6 : 2;
   else if (h->type == T_HNSW) rtype = 5;
-  else rtype = h->sq8 ? 3 : 4;
+  else
+    rtype = h->sq_bits == 8 ? 3 : h->sq_bits == 6 ? 8 : h->sq_bits == 4 ? 7 : 4;
   hipLaunchKernelGGL(k_reconstruct, dim3((unsigned)(nq * k)), dim3(64), 0,
                      (hipStream_t)stream, I_dev, nq, k, rtype, h->d, h->m,
                      h->dsub, h->stride, h->csr_arena.rlog, flat_src,
@@ -2710,8 +2731,8 @@ extern "C" int dfann_code_stride(dfann_index *h) { return h->stride; }
 extern "C" int dfann_get_sq_params(dfann_index *h, float *vmin_host,
                                    float *vdiff_host) {
   API_BEGIN
-  if (!((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq8))
-    throw std::runtime_error("not an 8-bit ivfsq index");
+  if (!((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq_int()))
+    throw std::runtime_error("not an 8 / 6 / 4-bit ivfsq index");
   HIP_CHECK(hipMemcpy(vmin_host, h->sq_vmin.p, (size_t)h->d * 4,
                       hipMemcpyDeviceToHost));
   HIP_CHECK(hipMemcpy(vdiff_host, h->sq_vdiff.p, (size_t)h->d * 4,
@@ -2742,7 +2763,7 @@ extern "C" int dfann_set_trained(dfann_index *h, const float *centroids_host,
                         (size_t)h->m * pq_ksub(h) * h->dsub * 4,
                         hipMemcpyHostToDevice));
   }
-  if (h->type == T_IVFSQ && h->sq8) {
+  if (h->type == T_IVFSQ && h->sq_int()) {
     if (!vmin_host || !vdiff_host) throw std::runtime_error("sq params required");
     h->sq_vmin.ensure((size_t)h->d * 4);
     h->sq_vdiff.ensure((size_t)h->d * 4);
@@ -2754,7 +2775,7 @@ extern "C" int dfann_set_trained(dfann_index *h, const float *centroids_host,
     std::vector<float> sc(h->d);
     std::vector<float> vd(h->d);
     memcpy(vd.data(), vdiff_host, (size_t)h->d * 4);
-    for (int t = 0; t < h->d; ++t) sc[t] = vd[t] / 255.0f;
+    for (int t = 0; t < h->d; ++t) sc[t] = vd[t] / h->sq_q();
     HIP_CHECK(hipMemcpy(h->sq_scale.p, sc.data(), (size_t)h->d * 4,
                         hipMemcpyHostToDevice));
   }
@@ -2874,7 +2895,11 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
     fwrite_chk(&jlen, 8, f);
     fwrite_chk(h->spec_json.data(), jlen, f);
     int32_t hdr[8] = {h->type, h->metric, h->d, h->nlist, h->m,
-                      h->nprobe, h->sq8 ? 1 : 0, h->stride};
+                      h->nprobe,
+                      // informational (the loader takes the width from the
+                      // spec): 0 fp16, 1 8-bit as ever, else the width
+                      h->sq_bits == 16 ? 0 : h->sq_bits == 8 ? 1 : h->sq_bits,
+                      h->stride};
     fwrite_chk(hdr, sizeof(hdr), f);
     uint8_t tr = h->trained ? 1 : 0;
     fwrite_chk(&tr, 1, f);
@@ -2886,7 +2911,7 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
         dump_dev(f, h->codebooks, (size_t)h->m * pq_ksub(h) * h->dsub * 4);
       if (h->opq)  // only when the spec carries "opq": older files are as before
         dump_dev(f, h->opq_A, (size_t)h->d * h->d_in * 4);
-      if ((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq8) {
+      if ((h->type == T_IVFSQ || h->type == T_HNSW) && h->sq_int()) {
         dump_dev(f, h->sq_vmin, (size_t)h->d * 4);
         dump_dev(f, h->sq_vdiff, (size_t)h->d * 4);
       }
@@ -2989,13 +3014,13 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
         opq_install(h, 0);
       }
       refresh_cent_bf16(h, 0);
-      if (h->type == T_IVFSQ && h->sq8) {
+      if (h->type == T_IVFSQ && h->sq_int()) {
         load_dev(f, h->sq_vmin, (size_t)h->d * 4);
         load_dev(f, h->sq_vdiff, (size_t)h->d * 4);
         std::vector<float> vd(h->d), sc(h->d);
         HIP_CHECK(hipMemcpy(vd.data(), h->sq_vdiff.p, (size_t)h->d * 4,
                             hipMemcpyDeviceToHost));
-        for (int t = 0; t < h->d; ++t) sc[t] = vd[t] / 255.0f;
+        for (int t = 0; t < h->d; ++t) sc[t] = vd[t] / h->sq_q();
         h->sq_scale.ensure((size_t)h->d * 4);
         HIP_CHECK(hipMemcpy(h->sq_scale.p, sc.data(), (size_t)h->d * 4,
                             hipMemcpyHostToDevice));

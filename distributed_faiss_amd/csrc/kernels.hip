@@ -1077,7 +1077,7 @@ extern "C" __global__ __launch_bounds__(256) void k_assign_rowblock(
 
 // ---------------------------------------------------------------------------
 // IVF list scan. One block per (query, probe). FAM: 0=PQ, 1=IVF-Flat,
-// 2=SQ8, 3=SQfp16. IP: minimize-key = -(bias + sum).
+// 2=SQ8 / SQ6 / SQ4 (SQB), 3=SQfp16. IP: minimize-key = -(bias + sum).
 // LDS: [fam region (fam_floats)] [SEL].
 // cand_d/cand_p: (nq, nprobe, k); pos = CSR row (uint32).
 // keys_dev: coarse minimize-keys (IP bias = -key); null for L2.
@@ -1314,6 +1314,106 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
   return acc;
 }
 
+// row sets in flight per wave in the SQ4 / SQ6 scans (ivf_scan_body)
+#ifndef DFANN_SQ4_UR
+#define DFANN_SQ4_UR 4
+#endif
+#ifndef DFANN_SQ6_UR
+#define DFANN_SQ6_UR 4
+#endif
+
+// SQ4 / SQ6 rows: a packed little-endian bit stream, B
+// bits per dimension. A lane's chunk is the 16 dims [t0, t0 + 16), t0 a
+// multiple of 16: 8 bytes at byte t0 / 2 (B = 4) or 12 bytes at byte
+// 3 * t0 / 4 (B = 6), i.e. 2 or 3 aligned dwords holding code b at bit
+// B * b. A dword is loaded only if it starts inside the row's code bytes
+// (ceil(d * B / 8)); the stride is a multiple of 16, so such a dword lies
+// wholly inside the row. That matters for B = 6: at d = 40 the row is 30
+// bytes in a 32-byte stride and lane 2's chunk would be bytes 24..35.
+template <int B>
+__device__ __forceinline__ void sqn_load(const uint8_t *__restrict__ cp, int t0,
+                                         int d, unsigned (&w)[3]) {
+  const int o = (t0 * B) >> 3;
+  if (B == 4) {
+    // o is a multiple of 8 below ceil(d / 2): the 8 bytes are in the stride
+    uint2 v = *reinterpret_cast<const uint2 *>(cp + o);
+    w[0] = v.x;
+    w[1] = v.y;
+    w[2] = 0u;
+    return;
+  }
+  const int cbytes = (d * B + 7) >> 3;
+  const unsigned *wp = reinterpret_cast<const unsigned *>(cp + o);
+  if (o + 12 <= cbytes) {  // the common case: one 12-byte load
+    w[0] = wp[0];
+    w[1] = wp[1];
+    w[2] = wp[2];
+  } else {  // the row's last chunk: only the dwords that hold a code
+    w[0] = wp[0];
+    w[1] = (o + 4 < cbytes) ? wp[1] : 0u;
+    w[2] = (o + 8 < cbytes) ? wp[2] : 0u;
+  }
+}
+
+// code b (compile-time) of a chunk: shift and mask, which the compiler
+// selects as v_bfe_u32; a 6-bit field that straddles two dwords (b = 5, 10)
+// takes the funnel of both
+template <int B>
+__device__ __forceinline__ unsigned sqn_code(const unsigned (&w)[3], int b) {
+  const int bit = B * b, lo = bit >> 5, sh = bit & 31;
+  unsigned v = w[lo] >> sh;
+  if (sh + B > 32) v |= w[lo + 1] << (32 - sh);
+  return v & ((1u << B) - 1u);
+}
+
+// one chunk's 16 terms added to `part` in ascending dimension order: the
+// SQ8 folded algebra (DFANN_PROC16_SQ8) with cf from the narrower code
+template <int B, bool IS_IP>
+__device__ __forceinline__ float sqn_accum(const unsigned (&w)[3], int t0,
+                                           int d, const float *ubuf,
+                                           const float *vbuf, float part) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    if (t0 + b < d) {
+      float cf = (float)sqn_code<B>(w, b);
+      int t = t0 + b;
+      if (IS_IP) {
+        part = part + (ubuf[t] + cf * vbuf[t]);
+      } else {
+        float diff = ubuf[t] - cf * vbuf[t];
+        part = part + diff * diff;
+      }
+    }
+  }
+  return part;
+}
+
+// The d <= 128 form: a lane's 16 dims never change, so its u / v terms sit
+// in registers (0 past d) and the 16 terms are straight-line code, with no
+// LDS read and no per-dimension branch. A dimension past d contributes
+// u = v = cf = 0 (pad bits are zero, unloaded dwords too): its term is +0,
+// and part + (+0) == part bitwise (part starts at +0 and +0 + -0 == +0, so
+// it is never -0). Same ascending order, same bits as the guarded form.
+template <int B, bool IS_IP>
+__device__ __forceinline__ float sqn_accum_reg(const unsigned (&w)[3],
+                                               const float (&ur)[16],
+                                               const float (&vr)[16],
+                                               float part) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int b = 0; b < 16; ++b) {
+    float cf = (float)sqn_code<B>(w, b);
+    if (IS_IP) {
+      part = part + (ur[b] + cf * vr[b]);
+    } else {
+      float diff = ur[b] - cf * vr[b];
+      part = part + diff * diff;
+    }
+  }
+  return part;
+}
+
 // Range selector: every row whose distance passes the
 // radius test, in ascending CSR position. A wave owns a contiguous run of
 // rows and its lanes hold them in ascending order, so a hit's rank is the
@@ -1353,7 +1453,7 @@ __device__ __forceinline__ void range_offer(RangeSel &r, bool valid, float val,
 }
 
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
-          bool N4, bool FILT, bool RANGE>
+          bool N4, bool FILT, bool RANGE, int SQB>
 __device__ void ivf_scan_body(
     const float *__restrict__ q, const float *__restrict__ cent,
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
@@ -1607,6 +1707,66 @@ __device__ void ivf_scan_body(
         }
       }
     }
+  } else if (FAM == 2 && SQB != 8) {
+    // SQ4 / SQ6: the SQ8 layout below with narrower rows.
+    // 8 lanes per row, lane l owning dims {16l + 128c + b}; a wave reads 8
+    // consecutive rows as 8 * stride contiguous bytes, 8 B (SQ4) or 12 B
+    // (SQ6) per lane and chunk. Same per-lane order, same butterfly, so the
+    // sum is bitwise the SQ8 one for the same cf.
+    const float *ubuf = fam, *vbuf = fam + d;
+    int g8 = threadIdx.x & 7, grp = SCAN_TID >> 3;
+    const bool onechunk = d <= 128;
+    const int NG8 = SCAN_NT >> 3;
+    // row sets in flight per wave (BASELINE.md "SQ4 / SQ6")
+    constexpr int UR = SQB == 4 ? DFANN_SQ4_UR : DFANN_SQ6_UR;
+    const int t0 = g8 * 16;
+    float ur[16], vr[16];  // d <= 128: the lane's terms, see sqn_accum_reg
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      bool in = onechunk && t0 + b < d;
+      ur[b] = in ? ubuf[t0 + b] : 0.f;
+      vr[b] = in ? vbuf[t0 + b] : 0.f;
+    }
+    for (long long base = SCAN_R0; base < SCAN_R1; base += (long long)NG8 * UR) {
+      if (!REGSEL) sel_guard(s, k, NG8 * UR);
+      unsigned wv[UR][3];
+      bool val[UR], ok[UR];  // FILT: ok = valid AND allowed (else == val)
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        long long pos = base + (long long)u * NG8 + grp;
+        val[u] = pos < SCAN_R1;
+        ok[u] = val[u];
+        if (FILT && val[u]) ok[u] = pos_allowed(posbits, pos);
+        wv[u][0] = wv[u][1] = wv[u][2] = 0u;
+        // d <= 128: every row set's loads are issued before any is used
+        if (onechunk && val[u] && t0 < d)
+          sqn_load<SQB>(slab_row(codes, rlog, pos, stride), t0, d, wv[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        long long pos = base + (long long)u * NG8 + grp;
+        float part = 0.f;
+        if (onechunk) {
+          part = sqn_accum_reg<SQB, IS_IP>(wv[u], ur, vr, part);
+        } else if (val[u]) {
+          const uint8_t *cp = slab_row(codes, rlog, pos, stride);
+          for (int tc = t0; tc < d; tc += 128) {
+            sqn_load<SQB>(cp, tc, d, wv[u]);
+            part = sqn_accum<SQB, IS_IP>(wv[u], tc, d, ubuf, vbuf, part);
+          }
+        }
+        part += __shfl_xor(part, 4, 8);
+        part += __shfl_xor(part, 2, 8);
+        part += __shfl_xor(part, 1, 8);
+        float dist = IS_IP ? -(bias + part) : part;
+        if (RANGE) {
+          range_offer<IS_IP>(rs, ok[u] && g8 == 0, IS_IP ? -dist : dist, pos);
+        } else if (ok[u] && g8 == 0) {
+          if (REGSEL) loc.push(dist, (unsigned)pos);
+          else sel_try(s, dist, (unsigned)pos);
+        }
+      }
+    }
   } else if (FAM == 2) {
     // SQ8: 8 lanes per row — a wave reads 8 consecutive rows as 1 KiB of
     // CONTIGUOUS lines (the streaming-copy access pattern) instead of 64
@@ -1806,7 +1966,7 @@ __device__ void ivf_scan_body(
 // needs (fan is forced to 1 for PRE / GLUT, which never split a list).
 //
 // DFANN_SCAN_MODES is the table, one row per mode:
-//   row(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)
+//   row(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4, SQB)
 // A row expands to k_scan_<NAME>_<l2|ip><SUFFIX>[_rk][_f]: metric x
 // {LDS-buffer selection, _rk register top-k (k <= 16)} x {plain, _f
 // filtered: FILT=true, rows tested against a.posbits}. XL2 rows have no
@@ -1818,6 +1978,8 @@ __device__ void ivf_scan_body(
 //   GLUT: LUT staged from HBM (built by k_pq_lut) instead of computed in
 //         the scan prologue; L16: those rows are __half (pq_lut_f16)
 //   N4:   4-bit PQ (nbits=4), in-kernel fp32 LUT only
+//   SQB:  bits per dimension of an integer SQ row (FAM 2): 8, or the
+//         packed 6 / 4; 8 on every other row, unread
 // _rg[_f]: range mode (RANGE=true). One kernel serves the
 // count and the fill pass (a.range_fill); it has the register path's row
 // loop (REGSEL=true) but no top-k state and no LDS beyond the fam region.
@@ -1849,9 +2011,9 @@ struct ScanArgs {
 };
 
 template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
-          bool N4, bool FILT, bool RANGE>
+          bool N4, bool FILT, bool RANGE, int SQB>
 __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
-  ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE>(
+  ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE, SQB>(
       a.q, a.cent, a.cb, a.sq_vmin, a.sq_scale, a.probes, a.keys, a.codes,
       a.off, a.nq, a.nprobe, a.d, a.m, a.dsub, a.k, a.stride, a.rlog,
       a.cand_d, a.cand_p, a.fam_floats, PRE ? a.term2 : nullptr,
@@ -1864,40 +2026,43 @@ __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
       RANGE ? a.range_I : nullptr, RANGE ? a.range_err : nullptr);
 }
 
-//  (MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)
+//  (MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4, SQB)
 #define DFANN_SCAN_MODES(X, XL2)                                               \
-  X(PQ, pq, , 0, false, false, false, false)         /* PQ8 in-kernel LUT */   \
-  XL2(PQ_PRE, pq, _pre, 0, true, false, false, false) /* PQ8 precomputed */    \
-  X(PQ_G, pq, _g, 0, false, true, false, false)      /* PQ8 GLUT f32 */        \
-  X(PQ_GH, pq, _gh, 0, false, true, true, false)     /* PQ8 GLUT f16 */        \
-  X(PQ4, pq4, , 0, false, false, false, true)        /* 4-bit PQ */            \
-  X(IVFFLAT, ivfflat, , 1, false, false, false, false)                         \
-  X(SQ8, sq8, , 2, false, false, false, false)                                 \
-  X(SQF, sqf, , 3, false, false, false, false)       /* SQ fp16 */
+  X(PQ, pq, , 0, false, false, false, false, 8)      /* PQ8 in-kernel LUT */   \
+  XL2(PQ_PRE, pq, _pre, 0, true, false, false, false, 8) /* PQ8 precomputed */ \
+  X(PQ_G, pq, _g, 0, false, true, false, false, 8)   /* PQ8 GLUT f32 */        \
+  X(PQ_GH, pq, _gh, 0, false, true, true, false, 8)  /* PQ8 GLUT f16 */        \
+  X(PQ4, pq4, , 0, false, false, false, true, 8)     /* 4-bit PQ */            \
+  X(IVFFLAT, ivfflat, , 1, false, false, false, false, 8)                      \
+  X(SQ8, sq8, , 2, false, false, false, false, 8)                              \
+  X(SQ6, sq6, , 2, false, false, false, false, 6)    /* packed 6-bit SQ */     \
+  X(SQ4, sq4, , 2, false, false, false, false, 4)    /* packed 4-bit SQ */     \
+  X(SQF, sqf, , 3, false, false, false, false, 8)    /* SQ fp16 */
 
 #define DFANN_SCAN_KERNEL(KNAME, FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, \
-                          RANGE)                                               \
+                          RANGE, SQB)                                          \
   extern "C" __global__ __launch_bounds__(512) void KNAME(ScanArgs a) {        \
-    scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE>(a);        \
+    scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE, SQB>(a);   \
   }
-#define DFANN_SCAN_METRIC(NAME, MET, SUFFIX, FAM, IS_IP, PRE, GLUT, L16, N4)   \
+#define DFANN_SCAN_METRIC(NAME, MET, SUFFIX, FAM, IS_IP, PRE, GLUT, L16, N4,   \
+                          SQB)                                                 \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX, FAM, IS_IP, false, PRE,     \
-                    GLUT, L16, N4, false, false)                               \
+                    GLUT, L16, N4, false, false, SQB)                          \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_f, FAM, IS_IP, false, PRE, \
-                    GLUT, L16, N4, true, false)                                \
+                    GLUT, L16, N4, true, false, SQB)                           \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk, FAM, IS_IP, true, PRE, \
-                    GLUT, L16, N4, false, false)                               \
+                    GLUT, L16, N4, false, false, SQB)                          \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rk_f, FAM, IS_IP, true,    \
-                    PRE, GLUT, L16, N4, true, false)                           \
+                    PRE, GLUT, L16, N4, true, false, SQB)                      \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rg, FAM, IS_IP, true, PRE, \
-                    GLUT, L16, N4, false, true)                                \
+                    GLUT, L16, N4, false, true, SQB)                           \
   DFANN_SCAN_KERNEL(k_scan_##NAME##_##MET##SUFFIX##_rg_f, FAM, IS_IP, true,    \
-                    PRE, GLUT, L16, N4, true, true)
-#define DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)         \
-  DFANN_SCAN_METRIC(NAME, l2, SUFFIX, FAM, false, PRE, GLUT, L16, N4)
-#define DFANN_SCAN_DEF(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)            \
-  DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4)               \
-  DFANN_SCAN_METRIC(NAME, ip, SUFFIX, FAM, true, PRE, GLUT, L16, N4)
+                    PRE, GLUT, L16, N4, true, true, SQB)
+#define DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4, SQB)    \
+  DFANN_SCAN_METRIC(NAME, l2, SUFFIX, FAM, false, PRE, GLUT, L16, N4, SQB)
+#define DFANN_SCAN_DEF(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4, SQB)       \
+  DFANN_SCAN_DEF_L2(MODE, NAME, SUFFIX, FAM, PRE, GLUT, L16, N4, SQB)          \
+  DFANN_SCAN_METRIC(NAME, ip, SUFFIX, FAM, true, PRE, GLUT, L16, N4, SQB)
 DFANN_SCAN_MODES(DFANN_SCAN_DEF, DFANN_SCAN_DEF_L2)
 #undef DFANN_SCAN_DEF
 #undef DFANN_SCAN_DEF_L2
@@ -2502,14 +2667,55 @@ extern "C" __global__ void k_codes_from_best4(const int *__restrict__ best,
   }
 }
 
-// SQ encode (8bit / fp16) of residuals
+// integer SQ code of one residual component: the 8-bit op sequence with
+// Q = 2^bits - 1 in place of 255 (truncation toward zero, then clamp)
+__device__ __forceinline__ unsigned sq_code(float v, float vmin, float vdiff,
+                                            float Q) {
+  float xi = (v - vmin) / vdiff;
+  int c = (int)(Q * xi);
+  int qi = (int)Q;
+  return (unsigned)(c < 0 ? 0 : (c > qi ? qi : c));
+}
+
+// SQ encode of residuals. bits: 16 = fp16, 8 = one byte per dimension,
+// 4 / 6 = packed little-endian bit stream (faiss Codec4bit / Codec6bit,
+// DESIGN.md §6h). The packed forms give each thread a whole byte (4-bit:
+// dims 2j, 2j+1) or a whole 3-byte group (6-bit: dims 4g .. 4g+3) of the
+// row's STRIDE, so no byte is shared between threads and every bit past
+// d * bits, pad bytes included, is written as zero.
 extern "C" __global__ void k_sq_encode(const float *__restrict__ resid,
                                        const float *__restrict__ vmin,
                                        const float *__restrict__ vdiff,
                                        long long n, int d, int stride,
-                                       int is_fp16, int rlog, long long row0,
+                                       int bits, int rlog, long long row0,
                                        uint8_t *const *__restrict__ codes) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (bits == 4 || bits == 6) {
+    const int per = bits == 4 ? stride : (stride + 2) / 3;  // units per row
+    const int dpu = bits == 4 ? 2 : 4;                      // dims per unit
+    const float Q = bits == 4 ? 15.0f : 63.0f;
+    long long total = n * per;
+    for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+      long long r = i / per;
+      int j = (int)(i % per);
+      const float *rv = resid + r * d;
+      unsigned word = 0;
+      for (int e = 0; e < dpu; ++e) {
+        int t = j * dpu + e;
+        if (t < d)
+          word |= sq_code(rv[t], vmin[t], vdiff[t], Q) << (e * bits);
+      }
+      uint8_t *row = slab_row_mut(codes, rlog, row0 + r, stride);
+      if (bits == 4) {
+        row[j] = (uint8_t)word;
+      } else {
+        for (int b = 0; b < 3; ++b)
+          if (3 * j + b < stride) row[3 * j + b] = (uint8_t)(word >> (8 * b));
+      }
+    }
+    return;
+  }
+  const int is_fp16 = bits == 16;
   long long total = n * d;
   for (; i < total; i += (long long)gridDim.x * blockDim.x) {
     long long r = i / d;
@@ -2763,7 +2969,7 @@ extern "C" __global__ void k_minmax_dims(const float *__restrict__ x, long long 
 
 extern "C" __global__ void k_minmax_decode(const unsigned *mn, const unsigned *mx,
                                            int d, float *vmin, float *vdiff,
-                                           float *scale) {
+                                           float *scale, float Q) {
   int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < d) {
     float lo = f32_dec(mn[t]), hi = f32_dec(mx[t]);
@@ -2771,14 +2977,15 @@ extern "C" __global__ void k_minmax_decode(const unsigned *mn, const unsigned *m
     if (df == 0.f) df = 1.0f;  // degenerate dim guard (oracle parity)
     vmin[t] = lo;
     vdiff[t] = df;
-    scale[t] = df / 255.0f;
+    scale[t] = df / Q;  // Q = 2^bits - 1: 255, 63 or 15
   }
 }
 
 // ---------------------------------------------------------------------------
 // reconstruction: decode result ids -> vectors. One block per (q, j).
 // type: 0 flat/ivfflat raw (flat_src != null uses flat arena directly by id,
-// else CSR codes row), 2 pq, 3 sq8, 4 sqfp16, 5 hnsw sq8, 6 pq nbits=4
+// else CSR codes row), 2 pq, 3 sq8, 4 sqfp16, 5 hnsw sq8, 6 pq nbits=4,
+// 7 sq4, 8 sq6 (packed bit streams)
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
@@ -2837,6 +3044,26 @@ extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
   } else if (type == 3) {  // sq8
     for (int t = threadIdx.x; t < d; t += blockDim.x) {
       unsigned c = cp[t];
+      out[t] = cent[(long long)L * d + t] + (vmin[t] + ((float)c + 0.5f) * scale[t]);
+    }
+  } else if (type == 7) {  // sq4: dim t in nibble t & 1 of byte t / 2
+    // (7 and 8 decode with separate mul and add, so that a reconstruction
+    // is bitwise the restated vmin + (c + 0.5) * scale; type 3 keeps the
+    // contraction it always had)
+    for (int t = threadIdx.x; t < d; t += blockDim.x) {
+#pragma clang fp contract(off)
+      unsigned c = (cp[t >> 1] >> ((t & 1) * 4)) & 15u;
+      out[t] = cent[(long long)L * d + t] + (vmin[t] + ((float)c + 0.5f) * scale[t]);
+    }
+  } else if (type == 8) {  // sq6: dim t at bit 6 * (t & 3) of 3-byte group t / 4
+    for (int t = threadIdx.x; t < d; t += blockDim.x) {
+#pragma clang fp contract(off)
+      // bytes past the row's last code byte are never read: byte b0 + 1 is
+      // needed only when the field crosses into it
+      int bit = (t & 3) * 6, b0 = (t >> 2) * 3 + (bit >> 3), sh = bit & 7;
+      unsigned w = cp[b0];
+      if (sh > 2) w |= (unsigned)cp[b0 + 1] << 8;
+      unsigned c = (w >> sh) & 63u;
       out[t] = cent[(long long)L * d + t] + (vmin[t] + ((float)c + 0.5f) * scale[t]);
     }
   } else {  // sqfp16

@@ -7,7 +7,7 @@
 # oracle. Engine spec keys:
 #   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq"
 #   dim, metric (0=IP, 1=L2), nlist, m, nbits (ivfpq: 4 | 8; DESIGN.md
-#   §6d), sq_type ("fp16"|"8bit"), nprobe, seed
+#   §6d), sq_type ("fp16"|"8bit"|"6bit"|"4bit"), nprobe, seed
 #   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
 #   (faiss IndexRefineFlat / IndexRefine)
 #   opq (1), opq_dim, opq_niter: learned orthonormal pre-transform in front
@@ -19,8 +19,9 @@
 #   * builder "knnlm" overwrites cfg.nprobe with the fresh index's default
 #     nprobe == 1 (reference index.py:47: cfg.nprobe = index.nprobe).
 #   * builder "ivfsq" uses the fp16 codec, not 8-bit (reference
-#     index.py:65); 8-bit SQ is reachable only via the factory string
-#     (e.g. "IVF{centroids},SQ8", reference tests/test_index_config.json).
+#     index.py:65); 8-, 6- and 4-bit SQ are reachable only via the factory
+#     string (e.g. "IVF{centroids},SQ8", reference
+#     tests/test_index_config.json).
 
 import math
 import re
@@ -106,9 +107,11 @@ def _builder_spec(cfg: IndexCfg) -> dict:
 # "OPQ<m>_<d_out>")
 _FACTORY_RE = re.compile(
     r"^(?:OPQ(?P<opq_m>\d+)(?:_(?P<opq_d>\d+))?,)?"
-    r"IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQfp16)"
+    r"IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQ6|SQ4|SQfp16)"
     r"(?:,(RFlat|Refine\(SQfp16\)))?)$")
 _FACTORY_REFINE = {"RFlat": "fp32", "Refine(SQfp16)": "fp16"}
+# faiss QT_8bit / QT_6bit / QT_4bit / QT_fp16 -> engine "sq_type"
+_FACTORY_SQ = {"SQ8": "8bit", "SQ6": "6bit", "SQ4": "4bit", "SQfp16": "fp16"}
 # "PQ<m>x<b>": bits per sub-quantizer code; "PQ<m>" is faiss's default 8
 PQ_NBITS_SUPPORTED = (4, 8)
 
@@ -158,7 +161,8 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if not mm:
         raise NotImplementedError(
             f"factory string {s!r} not supported; supported: Flat, IVFn,Flat, "
-            "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQfp16, "
+            "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQ6, IVFn,SQ4, "
+            "IVFn,SQfp16, "
             "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16), and "
             "the PQ forms preceded by OPQm, or OPQm_d, (same m)"
         )
@@ -168,7 +172,7 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if opq_m is not None and not kind.startswith("PQ"):
         raise NotImplementedError(
             f"factory string {s!r}: OPQ is supported in front of IVFn,PQm "
-            "only, not Flat / SQ8 / SQfp16"
+            "only, not Flat / SQ8 / SQ6 / SQ4 / SQfp16"
         )
     if kind == "Flat":
         spec.update(type="ivf_flat", nlist=nlist)
@@ -193,10 +197,8 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
                 spec["opq_dim"] = int(mm.group("opq_d"))
             if "opq_niter" in cfg.extra:
                 spec["opq_niter"] = int(cfg.extra["opq_niter"])
-    elif kind == "SQ8":
-        spec.update(type="ivfsq", nlist=nlist, sq_type="8bit")
     else:
-        spec.update(type="ivfsq", nlist=nlist, sq_type="fp16")
+        spec.update(type="ivfsq", nlist=nlist, sq_type=_FACTORY_SQ[kind])
     if mm.group(8):
         spec["refine"] = _FACTORY_REFINE[mm.group(8)]
         if "k_factor" in cfg.extra:

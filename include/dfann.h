@@ -72,7 +72,8 @@ typedef void *dfann_stream;             /* hipStream_t */
 
 /* Build an index from a JSON spec {"type": "flat"|"ivf_flat"|"ivfpq"|
  * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int,
- * "nbits": 4|8, "sq_type": "fp16"|"8bit", "nprobe": int, "seed": int}.
+ * "nbits": 4|8, "sq_type": "fp16"|"8bit"|"6bit"|"4bit", "nprobe": int,
+ * "seed": int}.
  * "ivfpq" codes: "nbits" (default 8) bits per sub-quantizer, 1 << nbits
  * codewords each; any other value is an error. At 8 a row is m bytes; at
  * 4 it is (m + 1) / 2 bytes, byte b = code[2b] |
@@ -82,6 +83,20 @@ typedef void *dfann_stream;             /* hipStream_t */
  * bits only the fp32 LUT built in the scan kernel exists: "pq_lut_f16",
  * "pq_lut_global": 1 and "pq_precomputed" are errors naming the knob
  * ("pq_lut_global": -1|0 and "pq_lut_mb" are accepted, without effect).
+ * "ivfsq" codes: "sq_type" (default "fp16"; a value not listed above is
+ * read as "fp16"). "fp16": 2 * dim bytes per row. "8bit" / "6bit" / "4bit"
+ * (faiss QT_8bit / QT_6bit / QT_4bit): B = 8 | 6 | 4 bits per
+ * dimension, code = clamp((int)(Q * (r - vmin) / vdiff), 0, Q) with Q =
+ * (1 << B) - 1 over per-dimension ranges of the training residuals
+ * (dfann_get_sq_params / dfann_set_trained carry vmin and vdiff at all
+ * three widths), decoded as vmin + (code + 0.5) * (vdiff / Q). A row is a
+ * little-endian bit stream of ceil(dim * B / 8) bytes, dimension t at bit
+ * B * t (faiss Codec8bit / Codec6bit / Codec4bit): at 4 bits byte t / 2
+ * holds dimension t in bits 4 * (t & 1); at 6 bits dimensions 4g .. 4g+3
+ * fill bytes 3g .. 3g+2, code i at bit 6i of that 24-bit little-endian
+ * word. Rows are padded to a multiple of 16 bytes (dfann_code_stride);
+ * every bit past dim * B, pad bytes included, is zero. "hnswsq" is always
+ * 8-bit.
  * Refine stage, "ivfpq" / "ivfsq" only (faiss IndexRefineFlat /
  * IndexRefine(SQfp16)): "refine": "fp32"|"fp16" (absent or
  * "" = off) keeps every added vector raw (round16(dim * 4 or 2) bytes per
@@ -98,7 +113,8 @@ typedef void *dfann_stream;             /* hipStream_t */
  * Replaces: faiss.IndexFlatIP/IndexFlatL2 (ref index.py:28-30,94),
  * faiss.IndexIVFFlat (ref index.py:38), faiss.IndexIVFPQ (ref
  * index.py:46), faiss.IndexIVFScalarQuantizer + QT_fp16/QT_8bit (ref
- * index.py:55,64-66), faiss.index_factory (ref index.py:396). */
+ * index.py:55,64-66; QT_6bit / QT_4bit through the factory string),
+ * faiss.index_factory (ref index.py:396). */
 int dfann_create(const char *spec_json, dfann_index **out);
 int dfann_destroy(dfann_index *h);
 
@@ -268,14 +284,15 @@ int dfann_transform_info(dfann_index *h, int64_t out[3]);
 int dfann_get_codebooks(dfann_index *h, float *out_host);
 /* Dump the finalized inverted lists to host: off (nlist+1 i64), ids
  * (ntotal i64, arrival ids in CSR order), codes (ntotal * stride u8).
- * stride = code_bytes rounded up to 16 (ivfpq nbits=4: nibble-packed rows,
- * see dfann_create). Used by the CPU-baseline leg of
+ * stride = code_bytes rounded up to 16 (ivfpq nbits=4 and ivfsq "6bit" /
+ * "4bit": packed rows, see dfann_create). Used by the CPU-baseline leg of
  * bench.py to scan the SAME index content the GPU holds. */
 int dfann_get_lists(dfann_index *h, int64_t *off_host, int64_t *ids_host,
                     uint8_t *codes_host);
 int dfann_code_stride(dfann_index *h);
 int dfann_get_sq_params(dfann_index *h, float *vmin_host,
-                        float *vdiff_host); /* (d,), (d,) */
+                        float *vdiff_host); /* (d,), (d,); ivfsq "8bit" /
+                                               "6bit" / "4bit" and hnswsq */
 
 /* --- shard-merge (replaces ResultHeap + _aggregate_results' arithmetic,
  *     ref client.py:29-54,265-310; fed by the RCCL all-gather of
