@@ -358,6 +358,7 @@ struct dfann_index {
   // workspace
   DevBuf ws1, ws2, ws3, ws4, ws5, ws_bf16a, ws_bf16b;
   DevBuf cent_bf16;
+  DevBuf chk_ws;  // one word for the input checks of train / add (§6i)
   DevBuf term2, term3_ws, qn_ws;  // PQ-L2 precomputed tables
   DevBuf pq_lut_ws;  // HBM ADC LUTs for the GLUT scan path
   // range search: results live here until the next range
@@ -536,6 +537,49 @@ static void assign_rows(dfann_index *h, const float *x, int64_t n,
 }
 
 // ---------------------------------------------------------------------------
+// input checks of train / add. Both end in a host read of
+// one word, so they sit where the caller synchronizes anyway.
+// ---------------------------------------------------------------------------
+
+// "NaN" / "Inf" when the array holds such a value, nullptr when all of it
+// is finite: k_absmax's unsigned maximum ranks NaN > Inf > finite by bit
+// pattern (the sign is cleared first).
+static const char *nonfinite_class(dfann_index *h, const float *x,
+                                   int64_t total, hipStream_t stream) {
+  if (total == 0) return nullptr;
+  h->chk_ws.ensure(8);
+  HIP_CHECK(hipMemsetAsync(h->chk_ws.p, 0, 4, stream));
+  hipLaunchKernelGGL(k_absmax, grid1d(total), dim3(256), 0, stream, x,
+                     (long long)total, h->chk_ws.as<unsigned>());
+  HIP_CHECK(hipGetLastError());
+  unsigned bits = 0;
+  HIP_CHECK(hipMemcpyAsync(&bits, h->chk_ws.p, 4, hipMemcpyDeviceToHost,
+                           stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (bits > 0x7F800000u) return "NaN";
+  if (bits == 0x7F800000u) return "Inf";
+  return nullptr;
+}
+
+// lowest row of a device assignment that is still -1, or -1 when every row
+// has a list
+static int64_t first_unassigned(dfann_index *h, const int32_t *assign_dev,
+                                int64_t n, hipStream_t stream) {
+  if (n == 0) return -1;
+  h->chk_ws.ensure(8);
+  HIP_CHECK(hipMemsetAsync(h->chk_ws.p, 0xFF, 8, stream));
+  hipLaunchKernelGGL(k_first_unassigned, grid1d(n), dim3(256), 0, stream,
+                     assign_dev, (long long)n,
+                     h->chk_ws.as<unsigned long long>());
+  HIP_CHECK(hipGetLastError());
+  unsigned long long first = 0;
+  HIP_CHECK(hipMemcpyAsync(&first, h->chk_ws.p, 8, hipMemcpyDeviceToHost,
+                           stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  return first == ~0ULL ? -1 : (int64_t)first;
+}
+
+// ---------------------------------------------------------------------------
 // k-means (restating faiss Clustering; deviations shared with the oracle —
 // oracle/__init__.py header): niter 25, strided subsample to k*256, seeded
 // partial-FY init, metric-driven assignment, mean update, deterministic
@@ -640,6 +684,15 @@ static void kmeans_device(dfann_index *h, const float *x, int64_t n, int kcent,
     HIP_CHECK(hipMemcpyAsync(h_counts.data(), counts.p, (size_t)kcent * 4,
                              hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
+    // every row joined a cluster? (k_centroid_accum skips a row whose
+    // assignment is still -1: finite values whose products overflow)
+    int64_t n_asg = 0;
+    for (int c = 0; c < kcent; ++c) n_asg += h_counts[c];
+    if (n_asg != nt)
+      throw std::runtime_error(
+          "train: k-means found no nearest centroid for " +
+          std::to_string(nt - n_asg) + " of " + std::to_string(nt) +
+          " rows (values too large for fp32 distances)");
     bool any_empty = false;
     for (int c = 0; c < kcent; ++c)
       if (h_counts[c] == 0) { any_empty = true; break; }
@@ -1123,6 +1176,12 @@ static void train_impl(dfann_index *h, int64_t n, const float *x,
     resid.ensure((size_t)n * h->d * 4);
     assign_rows(h, x, n, asg.as<int>(), stream);
     trace_point("train:assign", stream);
+    // all n rows are assigned here, not only the k-means subsample
+    int64_t bad = first_unassigned(h, asg.as<int>(), n, stream);
+    if (bad >= 0)
+      throw std::runtime_error(
+          "train: row " + std::to_string(bad) +
+          " has no nearest centroid (values too large for fp32 distances)");
     hipLaunchKernelGGL(k_residual, grid1d(n * h->d), dim3(256), 0, stream, x,
                        h->centroids.as<float>(), asg.as<int>(), n, h->d,
                        resid.as<float>());
@@ -1395,6 +1454,7 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
   const int64_t CH = std::max<int64_t>(
       65536, ((int64_t)h->ws_mb << 20) / std::max(4 * h->d, 1));
   DevBuf asg;
+  std::vector<int32_t> h_asg;
   for (int64_t s = 0; s < n; s += CH) {
     int64_t c = std::min(CH, n - s);
     asg.ensure((size_t)c * 4);
@@ -1408,13 +1468,26 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
       xi = h->opq_x.as<float>();
     }
     assign_rows(h, xi, c, asg.as<int>(), stream);
+    // The host copy of the assignments comes first: a row without a list
+    // (-1: a NaN row, or products that overflow) refuses the whole chunk
+    // before k_residual indexes a centroid by it and before rebuild_csr
+    // counts it. Nothing of the chunk is stored; earlier chunks stay.
+    h_asg.resize((size_t)c);
+    HIP_CHECK(hipMemcpyAsync(h_asg.data(), asg.p, (size_t)c * 4,
+                             hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (int64_t i = 0; i < c; ++i)
+      if ((uint32_t)h_asg[i] >= (uint32_t)h->nlist)
+        throw std::runtime_error(
+            "add: row " + std::to_string(s + i) +
+            " of the batch has no nearest centroid (NaN, or values too "
+            "large for fp32 distances); rows from " + std::to_string(s) +
+            " on were not added");
     int64_t row0 = (int64_t)h->h_pend_assign.size();
     encode_chunk(h, c, xi, asg.as<int>(), row0, stream);
     if (h->refine) refine_append(h, c, xs, stream);
-    size_t old = h->h_pend_assign.size();
-    h->h_pend_assign.resize(old + c);
-    HIP_CHECK(hipMemcpyAsync(h->h_pend_assign.data() + old, asg.p,
-                             (size_t)c * 4, hipMemcpyDeviceToHost, stream));
+    h->h_pend_assign.insert(h->h_pend_assign.end(), h_asg.begin(),
+                            h_asg.end());
     HIP_CHECK(hipStreamSynchronize(stream));
     h->ntotal += c;
     h->dirty = true;
@@ -1501,6 +1574,13 @@ static void hnsw_add(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream) {
   const int M = h->m, deg0 = 2 * h->m;
   const int64_t n0 = h->ntotal, ntot = n0 + n;
+  // A non-finite row would insert with NaN distances: an empty beam, so a
+  // node without links, and once its level makes it the entry point every
+  // later insert and query starts from that isolated node. Refused whole.
+  if (const char *cls = nonfinite_class(h, x, n * h->d, stream))
+    throw std::runtime_error(
+        std::string("add: the batch holds a non-finite value (") + cls +
+        "); hnswsq adds no row of it");
   // 1) encode rows [n0, ntot) into the code arena (arrival order; the
   //    HNSW arena is never rebuilt — ids ARE row positions)
   h->csr_arena.ensure_rows(ntot);
@@ -2040,6 +2120,7 @@ static ScanJob scan_prepare(dfann_index *h, int64_t nq, const float *q,
   a.sq_vmin = h->sq_vmin.as<float>();
   a.sq_scale = h->sq_scale.as<float>();
   a.off = h->cr_off.as<int64_t>();
+  a.nlist = h->nlist;
   a.nprobe = nprobe;
   a.d = h->d;
   a.m = h->m;
@@ -2114,12 +2195,14 @@ static void scan_launch(dfann_index *h, const ScanJob &j, int64_t nq,
       if (h->timing) el = h->ev_begin(stream);
       if (p.lut_f16) {
         hipLaunchKernelGGL(k_pq_lut_f16, lg, dim3(256), lut_lds, stream, a.q,
-                           a.cent, a.cb, a.probes, a.nq, nprobe, h->d, h->m,
-                           h->dsub, ip ? 1 : 0, h->pq_lut_ws.as<__half>());
+                           a.cent, a.cb, a.probes, h->nlist, a.nq, nprobe,
+                           h->d, h->m, h->dsub, ip ? 1 : 0,
+                           h->pq_lut_ws.as<__half>());
       } else {
         hipLaunchKernelGGL(k_pq_lut, lg, dim3(256), lut_lds, stream, a.q,
-                           a.cent, a.cb, a.probes, a.nq, nprobe, h->d, h->m,
-                           h->dsub, ip ? 1 : 0, h->pq_lut_ws.as<float>());
+                           a.cent, a.cb, a.probes, h->nlist, a.nq, nprobe,
+                           h->d, h->m, h->dsub, ip ? 1 : 0,
+                           h->pq_lut_ws.as<float>());
       }
       if (h->timing) h->ev_end(el, stream, h->ev_lut);
     }
@@ -2140,7 +2223,9 @@ static void scan_account(dfann_index *h, int64_t nq, int nprobe,
   std::vector<int32_t> hp((size_t)nq * nprobe);
   HIP_CHECK(hipMemcpy(hp.data(), probes, hp.size() * 4, hipMemcpyDeviceToHost));
   int64_t rows = 0;
-  for (int32_t L : hp) rows += h->h_off[L + 1] - h->h_off[L];
+  for (int32_t L : hp)  // a probe outside [0, nlist) is an empty slot
+    if ((uint32_t)L < (uint32_t)h->nlist)
+      rows += h->h_off[L + 1] - h->h_off[L];
   h->scan_rows += rows;
   h->scan_bytes += rows * h->stride;
 }
@@ -2343,6 +2428,23 @@ static void check_filter(dfann_index *h, const uint32_t *allow,
         " ids but the index holds " + std::to_string(h->ntotal));
 }
 
+// shared host checks of the two preassigned top-k entries (the range entry
+// bounds its nprobe in range_impl). The probe VALUES are not checked: that
+// would need a host sync, and the scans treat a probe outside [0, nlist)
+// as an empty slot.
+static void check_preassigned(int k, int nprobe) {
+  if (k > 512)
+    throw std::runtime_error("search_preassigned: k > 512 unsupported (k = " +
+                             std::to_string(k) + ")");
+  if (k < 1)
+    throw std::runtime_error("search_preassigned: k < 1 (k = " +
+                             std::to_string(k) + ")");
+  if (nprobe < 1 || nprobe > 512)
+    throw std::runtime_error(
+        "search_preassigned: nprobe must be in 1..512 (nprobe = " +
+        std::to_string(nprobe) + ")");
+}
+
 static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
                         float *D, int64_t *I, hipStream_t stream,
                         const uint32_t *allow = nullptr) {
@@ -2445,6 +2547,14 @@ extern "C" int dfann_train(dfann_index *h, int64_t n, const float *x_dev,
                            dfann_stream stream) {
   API_BEGIN
   hipStream_t s = (hipStream_t)stream;
+  // one pass over the raw rows before anything is learned from them: a
+  // non-finite value is refused and the index stays untrained (flat trains
+  // nothing, a trained index ignores the call)
+  if (!h->trained && h->type != T_FLAT)
+    if (const char *cls = nonfinite_class(h, x_dev, n * h->d_in, s))
+      throw std::runtime_error(
+          std::string("train: the training set holds a non-finite value (") +
+          cls + ")");
   if (h->opq && !h->trained) {
     // faiss IndexPreTransform::train: learn the transform on the raw rows
     // (kept as is when one was injected), then train the inner index on
@@ -2503,6 +2613,10 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   API_BEGIN
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
+  check_preassigned(k, nprobe);
+  if (nq == 0) return 0;
+  if (!probes_dev || !keys_dev)
+    throw std::runtime_error("search_preassigned: null probes / keys");
   hipStream_t s = (hipStream_t)stream;
   const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
@@ -2545,8 +2659,10 @@ extern "C" int dfann_search_preassigned_filtered(
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
   check_filter(h, allow_bits_dev, nbits);
-  if (k > 512) throw std::runtime_error("k > 512 unsupported");
+  check_preassigned(k, nprobe);
   if (nq == 0) return 0;
+  if (!probes_dev || !keys_dev)
+    throw std::runtime_error("search_preassigned: null probes / keys");
   hipStream_t s = (hipStream_t)stream;
   const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,

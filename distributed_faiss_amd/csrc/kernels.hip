@@ -1459,8 +1459,8 @@ __device__ void ivf_scan_body(
     const float *__restrict__ cb, const float *__restrict__ sq_vmin,
     const float *__restrict__ sq_scale, const int *__restrict__ probes,
     const float *__restrict__ keys, const uint8_t *const *__restrict__ codes,
-    const int64_t *__restrict__ off, int nq, int nprobe, int d, int m,
-    int dsub, int k, int stride, int rlog, float *__restrict__ cand_d,
+    const int64_t *__restrict__ off, int nlist, int nq, int nprobe, int d,
+    int m, int dsub, int k, int stride, int rlog, float *__restrict__ cand_d,
     unsigned *__restrict__ cand_p, int fam_floats,
     const float *__restrict__ term2, const float *__restrict__ term3,
     const float *__restrict__ qn, int fan, const float *__restrict__ glut,
@@ -1497,7 +1497,14 @@ __device__ void ivf_scan_body(
   int bp = rest / fan, seg = rest % fan;
   int L = probes[(long long)bq * nprobe + bp];
   long long out_base = (((long long)bq * nprobe + bp) * fan + seg) * k;
-  long long l0 = off[L], l1 = off[L + 1];
+  // A probe outside [0, nlist) is an empty slot: one
+  // unsigned compare, and the empty-list exits below end the block before
+  // keys, cent or term2 are read for it.
+  long long l0 = 0, l1 = 0;
+  if ((unsigned)L < (unsigned)nlist) {
+    l0 = off[L];
+    l1 = off[L + 1];
+  }
   long long len = l1 - l0;
   long long s0 = l0 + len * seg / fan;
   long long s1 = l0 + len * (seg + 1) / fan;
@@ -1990,6 +1997,7 @@ struct ScanArgs {
   const float *keys;
   const uint8_t *const *codes;
   const int64_t *off;
+  int nlist;  // probes outside [0, nlist) are empty slots
   int nq, nprobe, d, m, dsub, k, stride, rlog;
   float *cand_d;
   unsigned *cand_p;
@@ -2015,7 +2023,7 @@ template <int FAM, bool IS_IP, bool REGSEL, bool PRE, bool GLUT, bool L16,
 __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
   ivf_scan_body<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE, SQB>(
       a.q, a.cent, a.cb, a.sq_vmin, a.sq_scale, a.probes, a.keys, a.codes,
-      a.off, a.nq, a.nprobe, a.d, a.m, a.dsub, a.k, a.stride, a.rlog,
+      a.off, a.nlist, a.nq, a.nprobe, a.d, a.m, a.dsub, a.k, a.stride, a.rlog,
       a.cand_d, a.cand_p, a.fam_floats, PRE ? a.term2 : nullptr,
       PRE ? a.term3 : nullptr, PRE ? a.qn : nullptr,
       (PRE || GLUT || RANGE) ? 1 : a.fan, GLUT ? a.glut : nullptr,
@@ -2137,8 +2145,8 @@ __global__ __launch_bounds__(256) void k_range_lims(
 template <typename LUTT, int DSUB, bool PAIRED, bool IS_IP>
 __device__ __forceinline__ void pq_lut_body(
     const float *__restrict__ q, const float *__restrict__ cent,
-    const float *__restrict__ cb, const int *__restrict__ probes, int nq,
-    int nprobe, int d, int m, int dsub_rt, LUTT *__restrict__ out) {
+    const float *__restrict__ cb, const int *__restrict__ probes, int nlist,
+    int nq, int nprobe, int d, int m, int dsub_rt, LUTT *__restrict__ out) {
   const int dsub = DSUB > 0 ? DSUB : dsub_rt;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int pad = dsub | 1;  // odd stride -> gcd(pad, banks) == 1
@@ -2161,8 +2169,13 @@ __device__ __forceinline__ void pq_lut_body(
     if (IS_IP) {
       r_sm[rr * pad + t] = qv;
     } else {
+      // a probe outside [0, nlist) is an empty slot: its table is built
+      // from the bare query and the scan never stages it
       int L = probes[qp];
-      r_sm[rr * pad + t] = qv - cent[(size_t)L * d + (size_t)j * dsub + t];
+      float cv = 0.f;
+      if ((unsigned)L < (unsigned)nlist)
+        cv = cent[(size_t)L * d + (size_t)j * dsub + t];
+      r_sm[rr * pad + t] = qv - cv;
     }
   }
   __syncthreads();
@@ -2258,8 +2271,8 @@ __device__ __forceinline__ void pq_lut_body(
 // IS_IP is a compile-time flag: a runtime test inside the unrolled loops
 // gets if-converted, i.e. BOTH metrics computed per entry, then selected.
 #define DFANN_PQ_LUT_CASE(LUTT, DS, PAIRED, IP, OUT)                           \
-  pq_lut_body<LUTT, DS, PAIRED, IP>(q, cent, cb, probes, nq, nprobe, d, m,     \
-                                    dsub, OUT)
+  pq_lut_body<LUTT, DS, PAIRED, IP>(q, cent, cb, probes, nlist, nq, nprobe, d, \
+                                    m, dsub, OUT)
 #define DFANN_PQ_LUT_DISPATCH(LUTT, PAIRED, IP, OUT)                           \
   switch (dsub) {                                                              \
     case 2: DFANN_PQ_LUT_CASE(LUTT, 2, PAIRED, IP, OUT); break;                \
@@ -2273,7 +2286,8 @@ __device__ __forceinline__ void pq_lut_body(
 
 extern "C" __global__ __launch_bounds__(256) void k_pq_lut(
     const float *q, const float *cent, const float *cb, const int *probes,
-    int nq, int nprobe, int d, int m, int dsub, int is_ip, float *out) {
+    int nlist, int nq, int nprobe, int d, int m, int dsub, int is_ip,
+    float *out) {
   if (is_ip) {
     DFANN_PQ_LUT_DISPATCH(float, false, true, out)
   } else {
@@ -2283,7 +2297,8 @@ extern "C" __global__ __launch_bounds__(256) void k_pq_lut(
 
 extern "C" __global__ __launch_bounds__(256) void k_pq_lut_f16(
     const float *q, const float *cent, const float *cb, const int *probes,
-    int nq, int nprobe, int d, int m, int dsub, int is_ip, __half *out) {
+    int nlist, int nq, int nprobe, int d, int m, int dsub, int is_ip,
+    __half *out) {
   if (is_ip) {
     DFANN_PQ_LUT_DISPATCH(__half, true, true, out)
   } else {
@@ -2625,7 +2640,20 @@ extern "C" __global__ __launch_bounds__(256) void k_merge_shards_w(
 // encode / build kernels
 // ---------------------------------------------------------------------------
 
-// residual: out[i] = x[i] - cent[assign[i]]
+// lowest row whose assignment is still k_assign_init's -1 (no key of the
+// row was < FLT_MAX: a NaN row, or products that overflowed). *first is
+// all ones before launch and stays so when every row has a list. Runs
+// before anything indexes by the assignment.
+extern "C" __global__ void k_first_unassigned(
+    const int *__restrict__ assign, long long n,
+    unsigned long long *__restrict__ first) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < n; i += (long long)gridDim.x * blockDim.x)
+    if (assign[i] < 0) atomicMin(first, (unsigned long long)i);
+}
+
+// residual: out[i] = x[i] - cent[assign[i]]; the callers have checked that
+// every assign[r] is a list (k_first_unassigned, or add_impl's host copy)
 extern "C" __global__ void k_residual(const float *__restrict__ x,
                                       const float *__restrict__ cent,
                                       const int *__restrict__ assign,
@@ -2914,10 +2942,14 @@ extern "C" __global__ void k_centroid_accum(const float *__restrict__ x,
   for (; i < total; i += (long long)gridDim.x * blockDim.x) {
     long long r = i / d;
     int t = (int)(i % d);
+    // a row no key of which was < FLT_MAX keeps k_assign_init's -1: it
+    // joins no cluster, and the host sees sum(counts) != n (kmeans_device)
+    int a = assign[r];
+    if (a < 0) continue;
     long long v = __double2ll_rn((double)x[i] * scale);
     // two's-complement wrap makes the unsigned add a signed add
-    atomicAdd(&sums[(long long)assign[r] * d + t], (unsigned long long)v);
-    if (t == 0) atomicAdd(&counts[assign[r]], 1);
+    atomicAdd(&sums[(long long)a * d + t], (unsigned long long)v);
+    if (t == 0) atomicAdd(&counts[a], 1);
   }
 }
 
@@ -3219,9 +3251,11 @@ __global__ __launch_bounds__(256) void k_refine(
     part = part + __shfl_xor(part, 4, 16);
     part = part + __shfl_xor(part, 2, 16);
     part = part + __shfl_xor(part, 1, 16);
-    if (ok && g == 0) {
-      const float key = METRIC == 0 ? -part : part;
-      srt[r] = ((unsigned long long)f32_enc(key) << 32) |
+    // a key the base selectors would not admit either (NaN or +Inf, from a
+    // non-finite query) stays out: the slot is a pad, D is never NaN
+    const float key = METRIC == 0 ? -part : part;
+    if (ok && g == 0 && key < DFANN_FLT_MAX) {
+      srt[r] =((unsigned long long)f32_enc(key) << 32) |
                (unsigned long long)(unsigned)id;
     }
   }

@@ -55,6 +55,45 @@
  * round and 4 hot-started after (faiss 40 / 4), at most 65536 strided
  * training rows, and the polar factor by Newton-Schulz in fp64 on the GPU
  * instead of an SVD.
+ *
+ * Hostile input. A bad vector or probe gives pads or an
+ * error, never a read or write indexed by an unchecked value:
+ *  S1 a probe outside [0, nlist) (-1, nlist, INT32_MIN, INT32_MAX, ...) is an
+ *     EMPTY SLOT in every scan mode, in the LUT kernels and in both range
+ *     passes; the keys entry of such a slot is never read. dfann_coarse
+ *     reports a slot it cannot fill (a NaN row; a list whose key is not
+ *     < FLT_MAX) as probe -1 with key +FLT_MAX. Deviation: faiss asserts
+ *     key < nlist; here that would cost a host sync, so the slot is skipped
+ *     (as faiss search_preassigned skips -1).
+ *  S2 a query row holding a NaN returns all pads (I = -1, D = +FLT_MAX for
+ *     L2 / -FLT_MAX for IP) from every search entry and index type, zero
+ *     rows from dfann_search_reconstruct, zero hits from range search.
+ *  S3 a row holding +-Inf but no NaN returns a well-formed result: valid,
+ *     distinct ids first, pads last, D never NaN and monotone in the
+ *     metric's order (D may be +-Inf). Nothing more is promised.
+ *  S4 the other rows of the batch are not affected: they return bitwise
+ *     what they return with each bad row replaced by a zero row.
+ *  S5 dfann_search_preassigned[_filtered]: k in 1..512, 1 <= nprobe <= 512,
+ *     nq == 0 returns at once; the error names the argument.
+ *  A1 dfann_train refuses a training set holding a NaN or Inf ("train: the
+ *     training set holds a non-finite value (NaN|Inf)") before it learns
+ *     anything; the index stays untrained and a later clean train gives the
+ *     artifacts of a fresh index. Finite rows no centroid can be assigned to
+ *     (products overflow fp32) end in a "train:" error too. flat trains
+ *     nothing and accepts anything.
+ *  A2 dfann_add, ivf types: rows are taken in internal chunks of
+ *     max(65536, ws_mb MB / 4 dim) rows. A chunk with a row that has no
+ *     nearest centroid (a NaN row; products that overflow) is refused as a
+ *     whole — "add: row R of the batch has no nearest centroid", R the first
+ *     such row — with nothing of it stored; chunks before it stay and
+ *     ntotal counts them. Searches after a refused add return what they
+ *     did before, and a later clean add gives the lists of an index that
+ *     never saw the bad batch. An Inf row that does get a list is stored as
+ *     it is (faiss does the same); it cannot affect other rows. hnswsq
+ *     refuses any batch holding a NaN or Inf (such a node would get no links
+ *     and could become the entry point). flat stores anything; a NaN row
+ *     can never be returned. Deviation: faiss consumes the id of a bad row
+ *     and stores nothing; here the id is not consumed.
  */
 #ifndef DFANN_H
 #define DFANN_H
@@ -125,19 +164,22 @@ int dfann_destroy(dfann_index *h);
  * "opq" index it first learns the transform on the raw rows (faiss
  * OPQMatrix::train; skipped when one was injected), then trains the inner
  * index on the transformed set (faiss IndexPreTransform::train).
- * Deterministic: same rows and seed give a bitwise-identical transform. */
+ * Deterministic: same rows and seed give a bitwise-identical transform.
+ * Non-finite rows are refused (Hostile input, A1). */
 int dfann_train(dfann_index *h, int64_t n, const float *x_dev,
                 dfann_stream stream);
 
 /* Replaces faiss `Index.add` at ref index.py:425 (coarse assign + encode
- * + inverted-list append; ids = arrival order). */
+ * + inverted-list append; ids = arrival order). A chunk with an
+ * unassignable row is refused whole (Hostile input, A2). */
 int dfann_add(dfann_index *h, int64_t n, const float *x_dev,
               dfann_stream stream);
 
 /* --- search path ------------------------------------------------------ */
 
 /* Replaces faiss `Index.search` at ref index.py:257. D_dev: (nq,k) f32,
- * I_dev: (nq,k) i64. k <= 512 (see Limits above). */
+ * I_dev: (nq,k) i64. k <= 512 (see Limits above). NaN / Inf query rows:
+ * Hostile input, S2 - S4. */
 int dfann_search(dfann_index *h, int64_t nq, const float *q_dev, int k,
                  float *D_dev, int64_t *I_dev, dfann_stream stream);
 
@@ -154,13 +196,17 @@ int dfann_search_reconstruct(dfann_index *h, int64_t nq, const float *q_dev,
 
 /* Coarse quantization only: top-nprobe list ids (i32, (nq,nprobe)) and
  * their minimize-keys (f32; L2: |c|^2-2q.c, IP: -q.c). Mirrors the
- * quantizer search half of faiss IndexIVF::search. */
+ * quantizer search half of faiss IndexIVF::search. A slot that cannot be
+ * filled is probe -1 with key +FLT_MAX (Hostile input, S1). */
 int dfann_coarse(dfann_index *h, int64_t nq, const float *q_dev, int nprobe,
                  int32_t *probes_dev, float *keys_dev, dfann_stream stream);
 
 /* Search with externally supplied probe lists (+keys for the IP bias).
  * Mirrors faiss IndexIVF::search_preassigned; also the parity-test hook
- * for probe-set-independent bit-exactness. */
+ * for probe-set-independent bit-exactness.
+ * k in 1..512, 1 <= nprobe <= 512, nq == 0 returns at once (S5);
+ * probes_dev and keys_dev must not be NULL (as in the range entry). A probe
+ * outside [0, nlist) is an empty slot and its key is not read (S1). */
 int dfann_search_preassigned(dfann_index *h, int64_t nq, const float *q_dev,
                              int nprobe, const int32_t *probes_dev,
                              const float *keys_dev, int k, float *D_dev,
@@ -177,7 +223,7 @@ int dfann_search_preassigned(dfann_index *h, int64_t nq, const float *q_dev,
 int dfann_search_filtered(dfann_index *h, int64_t nq, const float *q_dev, int k,
                           const uint32_t *allow_bits_dev, int64_t nbits,
                           float *D_dev, int64_t *I_dev, dfann_stream stream);
-/* dfann_search_preassigned under the same filter. */
+/* dfann_search_preassigned under the same filter (same S1 / S5 rules). */
 int dfann_search_preassigned_filtered(dfann_index *h, int64_t nq,
         const float *q_dev, int nprobe, const int32_t *probes_dev,
         const float *keys_dev, int k, const uint32_t *allow_bits_dev,
@@ -212,7 +258,8 @@ int dfann_range_search(dfann_index *h, int64_t nq, const float *q_dev,
                        dfann_stream stream);
 /* The same over caller-supplied probe lists (dfann_coarse's probes and
  * keys). Mirrors faiss IndexIVF::range_search_preassigned. A list named
- * twice contributes its hits twice. 1 <= nprobe <= 512. */
+ * twice contributes its hits twice. 1 <= nprobe <= 512. A probe outside
+ * [0, nlist) contributes nothing in either pass (Hostile input, S1). */
 int dfann_range_search_preassigned(dfann_index *h, int64_t nq,
         const float *q_dev, int nprobe, const int32_t *probes_dev,
         const float *keys_dev, float radius, const uint32_t *allow_dev,
