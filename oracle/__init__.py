@@ -38,6 +38,24 @@
 #     within-list scans; cross-list tie order in faiss is heap-order
 #     dependent and unpinned).
 #
+# Engine-side options restated here (the engine's own contracts, not
+# faiss-cpu behaviour unless noted; each DEFINES a bit-exact tier of the
+# GPU suite and is checked on the CPU against an independent formula):
+#   - core.OracleIVFPQ(nbits=4|8): one class over ksub = 1 << nbits
+#     (DESIGN.md §6d); pack_pq4 / unpack_pq4 give the stored 4-bit rows;
+#   - core.OracleIVFSQ(qtype=fp16|8bit|6bit|4bit): one integer-codec path
+#     over Q = (1 << bits) - 1; pack_sq / unpack_sq give the
+#     stored 4- and 6-bit rows;
+#   - every IVF oracle: packed_lists() / load_lists() exchange inverted
+#     lists with an engine as stored bytes, and from_engine_artifacts()
+#     builds a trained oracle from an engine's centroids, codebooks or
+#     ranges and, optionally, its lists;
+#   - refine.py: the exact re-ranking stage;
+#   - range.py: range search over any IVF oracle's _scan_one (§6g);
+#   - opq.py: the OPQ pre-transform, OracleOPQ and the OPQ trainer (§6f).
+# make_oracle_engine builds the plain index of a spec and ignores the opq,
+# refine and k_factor keys.
+#
 # fp16-LUT tier (spec "pq_lut_f16"): OracleIVFPQ rounds every
 # ADC table entry to IEEE half once (numpy float16: round-to-nearest-even,
 # gradual underflow), widens it back to fp32 and sums sequentially in fp32
@@ -69,11 +87,30 @@ from .core import (  # noqa: F401
     OracleIVFFlat,
     OracleIVFPQ,
     OracleIVFSQ,
+    pack_pq4,
+    unpack_pq4,
+    pack_sq,
+    unpack_sq,
+    sq_code_bytes,
+    sq_stride,
     make_oracle_engine,
+    from_engine_artifacts,
     save_oracle_engine,
     load_oracle_engine,
     OracleProvider,
     aggregate_results,
     OracleHNSWSearch,
     OracleHNSWBuild,
+)
+from .opq import OracleOPQ  # noqa: F401
+from .range import (  # noqa: F401
+    range_from_scans,
+    range_search_ref,
+    ranking,
+    scan_lists,
+)
+from .refine import (  # noqa: F401
+    k_prime,
+    refine_distances,
+    refine_ref,
 )

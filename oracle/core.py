@@ -207,14 +207,88 @@ def seq_ip(q: np.ndarray, xs: np.ndarray) -> np.ndarray:
 def adc_scan(lut: np.ndarray, codes: np.ndarray) -> np.ndarray:
     """ADC distances: sum_j lut[j, codes[i, j]], sequential over j.
 
-    lut: (m, 256) fp32; codes: (n, m) uint8. fp32 accumulation, j ascending
-    — mirrored exactly by the HIP ivfpq scan kernel.
+    lut: (m, ksub) fp32; codes: (n, m) uint8. fp32 accumulation, j ascending
+    — mirrored exactly by the HIP ivfpq scan kernels.
     """
     n = codes.shape[0]
     acc = np.zeros(n, dtype=np.float32)
     for j in range(lut.shape[0]):
         acc = acc + lut[j, codes[:, j]]
     return acc
+
+
+# ---------------------------------------------------------------------------
+# Stored row formats of the sub-byte codes. In memory every oracle keeps
+# one code per uint8; these give the bytes the engine stores.
+#   PQ 4-bit: byte b = code[2b] | code[2b+1] << 4 (the faiss ProductQuantizer
+#     bit order); odd m leaves the last high nibble 0.
+#   SQ 4/6-bit: a little-endian bit stream (faiss Codec4bit / Codec6bit):
+#     4-bit: byte t // 2 holds dim t in bits 4 * (t & 1);
+#     6-bit: dims 4g .. 4g+3 in bytes 3g .. 3g+2, code i at bit 6i of that
+#            24-bit little-endian word;
+#     ceil(d * bits / 8) bytes per row, every bit past d * bits zero.
+# ---------------------------------------------------------------------------
+
+
+def pack_pq4(codes):
+    """(n, m) codes 0..15 -> (n, (m + 1) // 2) uint8 packed rows."""
+    codes = np.asarray(codes)
+    assert codes.ndim == 2 and (codes >= 0).all() and (codes < 16).all()
+    n, m = codes.shape
+    c = np.zeros((n, 2 * ((m + 1) // 2)), np.uint8)
+    c[:, :m] = codes
+    return (c[:, 0::2] | (c[:, 1::2] << 4)).astype(np.uint8)
+
+
+def unpack_pq4(packed, m):
+    """(n, >= (m + 1) // 2) packed rows -> (n, m) uint8 codes 0..15."""
+    packed = np.asarray(packed, np.uint8)[:, :(m + 1) // 2]
+    c = np.empty((packed.shape[0], 2 * packed.shape[1]), np.uint8)
+    c[:, 0::2] = packed & 15
+    c[:, 1::2] = packed >> 4
+    return c[:, :m]
+
+
+def sq_code_bytes(d, bits):
+    return (d * bits + 7) // 8
+
+
+def sq_stride(d, bits):
+    """The engine's row stride: code bytes rounded up to 16."""
+    return (sq_code_bytes(d, bits) + 15) // 16 * 16
+
+
+def pack_sq(codes, bits):
+    """(n, d) codes 0 .. 2^bits - 1 -> (n, ceil(d * bits / 8)) uint8 rows."""
+    codes = np.asarray(codes)
+    assert bits in (4, 6) and codes.ndim == 2
+    if (codes < 0).any() or (codes >= (1 << bits)).any():
+        raise ValueError(f"code out of range for {bits} bits")
+    n, d = codes.shape
+    out = np.zeros((n, sq_code_bytes(d, bits)), np.uint8)
+    for t in range(d):
+        c = codes[:, t].astype(np.uint32)
+        bit = t * bits  # position in the row's little-endian bit stream
+        by, sh = bit >> 3, bit & 7
+        out[:, by] |= ((c << sh) & 0xFF).astype(np.uint8)
+        if sh + bits > 8:
+            out[:, by + 1] |= (c >> (8 - sh)).astype(np.uint8)
+    return out
+
+
+def unpack_sq(packed, d, bits):
+    """(n, >= ceil(d * bits / 8)) packed rows -> (n, d) uint8 codes."""
+    packed = np.asarray(packed, np.uint8)
+    assert bits in (4, 6) and packed.shape[1] >= sq_code_bytes(d, bits)
+    out = np.empty((packed.shape[0], d), np.uint8)
+    for t in range(d):
+        bit = t * bits
+        by, sh = bit >> 3, bit & 7
+        w = packed[:, by].astype(np.uint32)
+        if sh + bits > 8:
+            w = w | (packed[:, by + 1].astype(np.uint32) << 8)
+        out[:, t] = (w >> sh) & ((1 << bits) - 1)
+    return out
 
 
 # ---------------------------------------------------------------------------
@@ -316,6 +390,28 @@ class _OracleIVFBase(_OracleIndexBase):
         rows = np.arange(q.shape[0])[:, None]
         return probes, sc[rows, probes]
 
+    # -- inverted lists as the engine stores them ---------------------------
+    # Each class names its per-list store (`_store`) and converts between
+    # its in-memory rows and the stored bytes (_to_bytes / _from_bytes).
+
+    def packed_lists(self):
+        """(off, ids, rows) in CSR order: rows are the stored bytes of every
+        row, (ntotal, code_bytes) uint8, without stride padding."""
+        off = np.zeros(self.nlist + 1, np.int64)
+        off[1:] = np.cumsum([len(i) for i in self.list_ids])
+        rows = np.concatenate(getattr(self, self._store))
+        return off, np.concatenate(self.list_ids), self._to_bytes(rows)
+
+    def load_lists(self, off, ids, rows):
+        """Take over inverted lists dumped by an engine; rows may carry the
+        engine's stride padding."""
+        data = self._from_bytes(np.asarray(rows, np.uint8))
+        self.list_ids = [np.asarray(ids[off[l]:off[l + 1]], np.int64)
+                         for l in range(self.nlist)]
+        setattr(self, self._store,
+                [data[off[l]:off[l + 1]] for l in range(self.nlist)])
+        self.ntotal = int(off[-1])
+
     # -- common search plumbing (per-class _scan_one(qi, li, bias)) --------
     # bias: None -> compute internally (seq_ip of q and the list centroid,
     # IP metric only); else the externally supplied coarse bias (parity
@@ -371,9 +467,17 @@ class _OracleIVFBase(_OracleIndexBase):
 class OracleIVFFlat(_OracleIVFBase):
     """faiss IndexIVFFlat restated (reference index.py:36-40)."""
 
+    _store = "list_data"
+
     def __init__(self, d, nlist, metric, seed=1234):
         super().__init__(d, nlist, metric, seed)
         self.list_data = [np.empty((0, d), dtype=np.float32) for _ in range(self.nlist)]
+
+    def _to_bytes(self, rows):
+        return np.ascontiguousarray(rows, np.float32).view(np.uint8)
+
+    def _from_bytes(self, rows):
+        return np.ascontiguousarray(rows[:, :4 * self.d]).view(np.float32)
 
     def train(self, x):
         self.centroids = kmeans(x, self.nlist, self.metric, self.seed,
@@ -438,23 +542,37 @@ class OracleIVFFlat(_OracleIVFBase):
 class OracleIVFPQ(_OracleIVFBase):
     """faiss IndexIVFPQ restated (reference index.py:43-48 'knnlm' builder).
 
-    Residual PQ (by_residual=true, faiss default), ksub=256, nbits=8 only.
-    codebooks: (m, 256, dsub) fp32. ADC LUT scan, LUT built per (query,
-    probe) from the residual q - centroid[probe].
+    Residual PQ (by_residual=true, faiss default), nbits 8 or 4 with
+    ksub = 1 << nbits codewords per sub-quantizer. codebooks: (m, ksub,
+    dsub) fp32. Codes are kept one per uint8, (n, m), at both widths (the
+    stored 4-bit rows: pack_pq4). ADC LUT scan, LUT built per (query,
+    probe) from the residual q - centroid[probe]; every LUT entry and every
+    encode distance is fp32, t ascending, separate mul and add.
     """
+
+    _store = "list_codes"
 
     def __init__(self, d, nlist, m, metric, nbits=8, seed=1234):
         super().__init__(d, nlist, metric, seed)
-        assert nbits == 8, "only 8-bit PQ codes supported (ksub=256)"
+        assert nbits in (4, 8), "PQ codes are 4 or 8 bits wide"
         assert d % m == 0, f"dim {d} not divisible by m={m}"
         self.m = int(m)
         self.dsub = d // m
+        self.nbits = int(nbits)
+        self.ksub = 1 << self.nbits
         self.codebooks = None
-        # spec "pq_lut_f16": every ADC table entry is rounded to IEEE half
-        # once (round-to-nearest-even, gradual underflow) and widened back
-        # before the fp32 sequential sum — the engine's fp16-LUT scan
+        # spec "pq_lut_f16" (8-bit codes only): every ADC table entry is
+        # rounded to IEEE half once (round-to-nearest-even, gradual
+        # underflow) and widened back before the fp32 sequential sum — the
+        # engine's fp16-LUT scan. There are no fp16 tables at 4 bits.
         self.lut_f16 = False
         self.list_codes = [np.empty((0, m), dtype=np.uint8) for _ in range(self.nlist)]
+
+    def _to_bytes(self, codes):
+        return pack_pq4(codes) if self.nbits == 4 else codes
+
+    def _from_bytes(self, rows):
+        return unpack_pq4(rows, self.m) if self.nbits == 4 else rows[:, :self.m]
 
     def train(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -462,16 +580,17 @@ class OracleIVFPQ(_OracleIVFBase):
                                 max_points_per_centroid=self.max_ppc)
         assign = assign_batch(x, self.centroids, self.metric)
         resid = x - self.centroids[assign]
-        cb = np.empty((self.m, 256, self.dsub), dtype=np.float32)
+        cb = np.empty((self.m, self.ksub, self.dsub), dtype=np.float32)
         for j in range(self.m):
             sub = resid[:, j * self.dsub : (j + 1) * self.dsub]
-            cb[j] = kmeans(sub, 256, METRIC_L2, self.seed + 1 + j,
+            cb[j] = kmeans(sub, self.ksub, METRIC_L2, self.seed + 1 + j,
                            max_points_per_centroid=self.max_ppc)
         self.codebooks = cb
         self.is_trained = True
 
     def encode(self, x):
-        """(assign, codes): coarse assignment + per-subspace argmin codes."""
+        """(assign, codes): coarse assignment + per-subspace argmin codes
+        (lowest index on ties)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         assign = assign_batch(x, self.centroids, self.metric)
         resid = x - self.centroids[assign]
@@ -482,7 +601,7 @@ class OracleIVFPQ(_OracleIVFBase):
             sub = resid[:, j * self.dsub : (j + 1) * self.dsub]
             for s in range(0, x.shape[0], 65536):
                 ss = sub[s : s + 65536]
-                acc = np.zeros((ss.shape[0], 256), dtype=np.float32)
+                acc = np.zeros((ss.shape[0], self.ksub), dtype=np.float32)
                 for t in range(self.dsub):
                     diff = ss[:, t, None] - self.codebooks[j][None, :, t]
                     acc = acc + diff * diff
@@ -502,24 +621,24 @@ class OracleIVFPQ(_OracleIVFBase):
         self.ntotal += x.shape[0]
 
     def build_lut(self, qi: np.ndarray, li: int):
-        """(lut, bias) for one (query, probe). L2: lut[j,c] = ||r_j - cb||^2
-        seq over dsub, bias=0. IP: lut[j,c] = q_j . cb, bias = q . centroid.
+        """(lut (m, ksub), bias) for one (query, probe). L2: lut[j,c] =
+        ||r_j - cb||^2 seq over dsub, bias=0. IP: lut[j,c] = q_j . cb,
+        bias = q . centroid.
         """
+        lut = np.empty((self.m, self.ksub), dtype=np.float32)
         if self.metric == METRIC_L2:
             r = qi - self.centroids[li]
-            lut = np.empty((self.m, 256), dtype=np.float32)
             for j in range(self.m):
                 rs = r[j * self.dsub : (j + 1) * self.dsub]
-                acc = np.zeros(256, dtype=np.float32)
+                acc = np.zeros(self.ksub, dtype=np.float32)
                 for t in range(self.dsub):
                     diff = np.float32(rs[t]) - self.codebooks[j][:, t]
                     acc = acc + diff * diff
                 lut[j] = acc
             return lut, np.float32(0.0)
-        lut = np.empty((self.m, 256), dtype=np.float32)
         for j in range(self.m):
             qs = qi[j * self.dsub : (j + 1) * self.dsub]
-            acc = np.zeros(256, dtype=np.float32)
+            acc = np.zeros(self.ksub, dtype=np.float32)
             for t in range(self.dsub):
                 acc = acc + np.float32(qs[t]) * self.codebooks[j][:, t]
             lut[j] = acc
@@ -576,50 +695,73 @@ class OracleIVFPQ(_OracleIVFBase):
 
 class OracleIVFSQ(_OracleIVFBase):
     """faiss IndexIVFScalarQuantizer restated (reference index.py:63-68:
-    QT_fp16 builder 'ivfsq'; QT_8bit reachable via the factory string path,
-    e.g. "IVF{centroids},SQ8" — reference tests/test_index_config.json).
+    QT_fp16 builder 'ivfsq'; the integer codecs reachable via the factory
+    string path, e.g. "IVF{centroids},SQ8" — reference
+    tests/test_index_config.json).
 
-    Residual encoding (faiss ctor default encode_residual=true). 8-bit codec:
-    per-dim [vmin, vmin+vdiff] trained on residual min/max; code =
-    clip(int(255 * (x-vmin)/vdiff), 0, 255); decode = vmin + (code+0.5) *
-    (vdiff/255). fp16 codec: IEEE half round-trip of the residual.
+    Residual encoding (faiss ctor default encode_residual=true). Integer
+    codecs, qtype "8bit" | "6bit" | "4bit", Q = (1 << bits) - 1: per-dim
+    [vmin, vmin+vdiff] trained on residual min/max (vdiff == 0 -> 1); code =
+    clip(int(Q * (x-vmin)/vdiff), 0, Q), truncating; decode = vmin +
+    (code+0.5) * (vdiff/Q). Codes are kept one per uint8, (n, d), at every
+    width (the stored 4- and 6-bit rows: pack_sq). fp16 codec: IEEE half
+    round-trip of the residual.
     """
+
+    _store = "list_codes"
+    _BITS = {"fp16": None, "8bit": 8, "6bit": 6, "4bit": 4}
 
     def __init__(self, d, nlist, metric, qtype="fp16", seed=1234):
         super().__init__(d, nlist, metric, seed)
-        assert qtype in ("fp16", "8bit")
+        assert qtype in self._BITS
         self.qtype = qtype
-        self.vmin = None    # (d,) fp32, 8bit only
-        self.scale = None   # (d,) fp32 = vdiff/255
+        self.bits = self._BITS[qtype]
+        self.vmin = None    # (d,) fp32, integer codecs only
         self.vdiff = None
-        code_bytes = 2 * d if qtype == "fp16" else d
-        self.code_bytes = code_bytes
-        self.list_codes = [np.empty((0, code_bytes), dtype=np.uint8) for _ in range(self.nlist)]
+        self.scale = None   # (d,) fp32 = vdiff/Q
+        if self.bits is None:
+            self.code_bytes = width = 2 * d
+        else:
+            self.Q = np.float32((1 << self.bits) - 1)
+            self.code_bytes = sq_code_bytes(d, self.bits)  # as stored
+            width = d
+        self.list_codes = [np.empty((0, width), dtype=np.uint8) for _ in range(self.nlist)]
+
+    def _to_bytes(self, codes):
+        return pack_sq(codes, self.bits) if self.bits in (4, 6) else codes
+
+    def _from_bytes(self, rows):
+        if self.bits in (4, 6):
+            return unpack_sq(rows, self.d, self.bits)
+        return rows[:, :self.code_bytes]
+
+    def set_ranges(self, vmin, vdiff):
+        self.vmin = np.ascontiguousarray(vmin, np.float32)
+        self.vdiff = np.ascontiguousarray(vdiff, np.float32)
+        self.scale = (self.vdiff / self.Q).astype(np.float32)
 
     def train(self, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
         self.centroids = kmeans(x, self.nlist, self.metric, self.seed,
                                 max_points_per_centroid=self.max_ppc)
-        if self.qtype == "8bit":
+        if self.bits is not None:
             assign = assign_batch(x, self.centroids, self.metric)
             resid = x - self.centroids[assign]
             vmin = resid.min(axis=0).astype(np.float32)
-            vmax = resid.max(axis=0).astype(np.float32)
-            self.vmin = vmin
-            self.vdiff = (vmax - vmin).astype(np.float32)
-            self.vdiff[self.vdiff == 0] = np.float32(1.0)  # degenerate dim guard
-            self.scale = (self.vdiff / np.float32(255.0)).astype(np.float32)
+            vdiff = (resid.max(axis=0).astype(np.float32) - vmin).astype(np.float32)
+            vdiff[vdiff == 0] = np.float32(1.0)  # degenerate dim guard
+            self.set_ranges(vmin, vdiff)
         self.is_trained = True
 
     def _encode_resid(self, resid):
-        if self.qtype == "fp16":
+        if self.bits is None:
             return resid.astype(np.float16).view(np.uint8).reshape(resid.shape[0], -1)
+        resid = np.asarray(resid, np.float32)
         xi = (resid - self.vmin[None, :]) / self.vdiff[None, :]
-        code = np.clip((np.float32(255.0) * xi).astype(np.int32), 0, 255).astype(np.uint8)
-        return code
+        return np.clip((self.Q * xi).astype(np.int32), 0, int(self.Q)).astype(np.uint8)
 
     def _decode_codes(self, codes):
-        if self.qtype == "fp16":
+        if self.bits is None:
             return codes.view(np.float16).astype(np.float32).reshape(codes.shape[0], self.d)
         return self.vmin[None, :] + (codes.astype(np.float32) + np.float32(0.5)) * self.scale[None, :]
 
@@ -642,9 +784,10 @@ class OracleIVFSQ(_OracleIVFBase):
         codes = self.list_codes[li]
         if codes.shape[0] == 0:
             return None
-        if self.qtype == "8bit":
+        if self.bits is not None:
             # folded decode algebra + 8-lane butterfly order, op-for-op the
-            # HIP scan kernel (csrc/kernels.hip FAM==2 subgroup-8 branch):
+            # HIP scan kernel (csrc/kernels.hip FAM==2 subgroup-8 branch),
+            # at every integer width with cf = float(code):
             # L2 diff = u - c*v with u = (q-cent-vmin) - 0.5*scale,
             # v = scale; IP term = u + c*v with u = q*vmin + 0.5*(q*scale),
             # v = q*scale. Lane l sums dims {l*16 + 128*c + b} sequentially;
@@ -661,20 +804,17 @@ class OracleIVFSQ(_OracleIVFBase):
                     diff = u[t] - cf[:, t] * v[t]
                     return diff * diff
             else:
-                qsc = (qi * self.scale).astype(np.float32)
-                uip = qi * self.vmin + np.float32(0.5) * qsc
+                v = (qi * self.scale).astype(np.float32)
+                u = qi * self.vmin + np.float32(0.5) * v
 
                 def term(t):
-                    return uip[t] + cf[:, t] * qsc[t]
+                    return u[t] + cf[:, t] * v[t]
 
-            n = codes.shape[0]
-            parts = [np.zeros(n, dtype=np.float32) for _ in range(8)]
+            parts = [np.zeros(codes.shape[0], dtype=np.float32) for _ in range(8)]
             for lane in range(8):
                 for t0 in range(lane * 16, self.d, 128):
-                    for b in range(16):
-                        t = t0 + b
-                        if t < self.d:
-                            parts[lane] = parts[lane] + term(t)
+                    for t in range(t0, min(t0 + 16, self.d)):
+                        parts[lane] = parts[lane] + term(t)
             acc = ((parts[0] + parts[4]) + (parts[2] + parts[6])) + (
                 (parts[1] + parts[5]) + (parts[3] + parts[7]))
             if self.metric == METRIC_L2:
@@ -721,9 +861,7 @@ class OracleIVFSQ(_OracleIVFBase):
         self.centroids = st["centroids"].astype(np.float32)
         vmin = st["vmin"]
         if vmin.size:
-            self.vmin = vmin.astype(np.float32)
-            self.vdiff = st["vdiff"].astype(np.float32)
-            self.scale = (self.vdiff / np.float32(255.0)).astype(np.float32)
+            self.set_ranges(vmin, st["vdiff"])
         self.list_codes = list(st["list_codes"])
         self.list_ids = list(st["list_ids"])
         self.ntotal = int(st["ntotal"])
@@ -740,7 +878,14 @@ def make_oracle_engine(spec: dict):
     """Build an oracle index from the engine spec dict.
 
     spec keys: type (flat|ivf_flat|ivfpq|ivfsq), dim, metric (0|1), nlist,
-    m, nbits, sq_type, nprobe, seed, max_ppc, pq_lut_f16.
+    m, nbits (4|8), sq_type (fp16|8bit|6bit|4bit), nprobe, seed, max_ppc,
+    pq_lut_f16 (8-bit PQ only; there are no fp16 tables at 4 bits).
+
+    The keys opq, refine and k_factor are IGNORED: the object built is the
+    plain index of the spec's type. The restatements of those stages are
+    separate (oracle.opq.OracleOPQ wraps an index; oracle.refine.refine_ref
+    re-ranks a candidate list), and the CPU tests of the Python layer run
+    an Index over this engine with those keys set.
     """
     t = spec["type"]
     d = int(spec["dim"])
@@ -753,7 +898,7 @@ def make_oracle_engine(spec: dict):
     elif t == "ivfpq":
         eng = OracleIVFPQ(d, int(spec["nlist"]), int(spec["m"]), metric,
                           int(spec.get("nbits", 8)), seed)
-        eng.lut_f16 = int(spec.get("pq_lut_f16", 0)) != 0
+        eng.lut_f16 = eng.nbits == 8 and int(spec.get("pq_lut_f16", 0)) != 0
     elif t == "ivfsq":
         eng = OracleIVFSQ(d, int(spec["nlist"]), metric, spec.get("sq_type", "fp16"), seed)
     else:
@@ -763,6 +908,27 @@ def make_oracle_engine(spec: dict):
         eng.max_ppc = int(spec.get("max_ppc", 256))
     eng.spec = dict(spec)
     return eng
+
+
+def from_engine_artifacts(spec, centroids, codebooks=None, vmin=None,
+                          vdiff=None, lists=None):
+    """A trained IVF oracle that shares an engine's trained artifacts (plain
+    numpy arrays: this package never sees an engine object).
+
+    lists: None -> empty, the caller adds; else (off, ids, rows) as an
+    engine's get_lists() returns them, stride padding included — the oracle
+    then scans the engine's own inverted lists.
+    """
+    orc = make_oracle_engine(spec)
+    orc.centroids = np.ascontiguousarray(centroids, np.float32)
+    if codebooks is not None:
+        orc.codebooks = np.ascontiguousarray(codebooks, np.float32)
+    if vmin is not None:
+        orc.set_ranges(vmin, vdiff)
+    orc.is_trained = True
+    if lists is not None:
+        orc.load_lists(*lists)
+    return orc
 
 
 def save_oracle_engine(eng, path: str):

@@ -1,8 +1,8 @@
-# Test-side restatement of the OPQ pre-transform (spec "opq": 1; DESIGN.md
+# ORACLE opq — restatement of the OPQ pre-transform (spec "opq": 1; DESIGN.md
 # §6f): faiss IndexPreTransform(OPQMatrix(d, M, d2), IndexIVFPQ).
 #
-#  * OracleOPQ wraps the existing IVFPQ restatement (oracle.OracleIVFPQ at 8
-#    bits, tests/pq4_ref.OraclePQ4 at 4) at d_out behind a matrix A
+#  * OracleOPQ wraps the IVFPQ restatement (core.OracleIVFPQ, 8 or 4 bits)
+#    at d_out behind a matrix A
 #    (d_out, d_in): y = A x, no bias. The transform itself is computed in
 #    float64 and rounded once — exact whenever A is a signed permutation /
 #    selection (one non-zero of magnitude 1 per row), which is what the
@@ -14,8 +14,7 @@
 #    (numpy.linalg.svd polar factor).
 import numpy as np
 
-from oracle.core import METRIC_L2, OracleIVFPQ, assign_batch, kmeans
-from pq4_ref import OraclePQ4
+from .core import METRIC_L2, OracleIVFPQ, assign_batch, kmeans
 
 
 def transform64(A, x):
@@ -57,10 +56,7 @@ class OracleOPQ:
     def __init__(self, A, nlist, m, metric, nbits=8, seed=1234):
         self.A = np.ascontiguousarray(A, np.float32)
         self.d_out, self.d_in = self.A.shape
-        if nbits == 4:
-            self.inner = OraclePQ4(self.d_out, nlist, m, metric, seed)
-        else:
-            self.inner = OracleIVFPQ(self.d_out, nlist, m, metric, 8, seed)
+        self.inner = OracleIVFPQ(self.d_out, nlist, m, metric, nbits, seed)
         self.nbits = nbits
 
     def set_trained(self, centroids, codebooks):
@@ -85,12 +81,7 @@ class OracleOPQ:
 
     def lists(self):
         """(off, ids, code bytes per row as the engine packs them)."""
-        if self.nbits == 4:
-            return self.inner.packed_lists()
-        off = np.zeros(self.inner.nlist + 1, np.int64)
-        off[1:] = np.cumsum([len(i) for i in self.inner.list_ids])
-        return (off, np.concatenate(self.inner.list_ids),
-                np.concatenate(self.inner.list_codes))
+        return self.inner.packed_lists()
 
 
 # ---------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-# Test-side restatement of range search over the CPU oracle.
+# ORACLE range — restatement of range search over the IVF
+# oracles of oracle/core.py.
 #
 # For each query and probe slot, in slot order, the oracle's own
 # `_scan_one(q, list, bias)` gives the list's distances (squared L2, or the
@@ -7,11 +8,11 @@
 # radius) and the optional allow mask pick the hits. Concatenated, that is
 # (lims, D, I) in the contract's order — probe slot, then ascending arrival
 # id — with the oracle's bit-exact float32 distances. A list named twice
-# contributes twice. `orc` is any oracle IVF index (oracle.core, or
-# tests/pq4_ref.OraclePQ4; `lut_f16` is the oracle's own option).
+# contributes twice. `orc` is any oracle IVF index (`lut_f16` is the
+# oracle's own option).
 import numpy as np
 
-from oracle.core import METRIC_L2
+from .core import METRIC_L2
 
 
 def scan_lists(orc, q, probes, keys):

@@ -1,4 +1,4 @@
-# Test-side restatement of the engine's refine stage (k_refine in
+# ORACLE refine — restatement of the engine's refine stage (k_refine in
 # csrc/kernels.hip), op for op in float32, so the GPU tests
 # can compare D and I bitwise.
 #

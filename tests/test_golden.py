@@ -40,3 +40,12 @@ def test_oracle_matches_golden(name):
         np.testing.assert_array_equal(D_, z["D"])  # bitwise: same code path
         if "centroids" in z.files:
             np.testing.assert_array_equal(eng.centroids, z["centroids"])
+        if "packed" in z.files:
+            np.testing.assert_array_equal(eng.packed_lists()[2], z["packed"])
+        if "lims" in z.files:
+            lims, RD, RI = MG.range_result(eng, q)
+            np.testing.assert_array_equal(lims, z["lims"])
+            np.testing.assert_array_equal(RI, z["RI"])
+            assert RD.dtype == z["RD"].dtype == np.float32
+            np.testing.assert_array_equal(RD.view(np.uint32),
+                                          z["RD"].view(np.uint32))

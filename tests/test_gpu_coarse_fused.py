@@ -19,25 +19,19 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
 from distributed_faiss_amd.hip_engine import HipEngine  # noqa: E402
+from gpu_support import assert_bitwise, bf16_round  # noqa: E402
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
 NORTH_STAR = 1e-4  # the project's relative bound
 KNOB = "DFANN_COARSE_FUSED"
-
-
-def _bf16_round(a):
-    """k_f32_to_bf16's integer formula: (u + 0x7FFF + lsb) >> 16."""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    lsb = (u >> np.uint64(16)) & np.uint64(1)
-    r = ((u + np.uint64(0x7FFF) + lsb) >> np.uint64(16)) & np.uint64(0xFFFF)
-    return (r << np.uint64(16)).astype(np.uint32).view(np.float32)
 
 
 def _both_paths(cent, q, metric, nprobe):
@@ -60,9 +54,8 @@ def _both_paths(cent, q, metric, nprobe):
 
 
 def _assert_bitwise_equal(fused, two_pass):
-    np.testing.assert_array_equal(fused[0], two_pass[0])
-    np.testing.assert_array_equal(fused[1].view(np.uint32),
-                                  two_pass[1].view(np.uint32))
+    """(probes, keys) pairs: ids equal, keys equal as bits."""
+    assert_bitwise(fused[1], fused[0], two_pass[1], two_pass[0])
 
 
 def _assert_fp64(cent, q, metric, probes, keys):
@@ -70,8 +63,8 @@ def _assert_fp64(cent, q, metric, probes, keys):
     nlist = cent.shape[0]
     # fp64 reference over the operands the GEMM consumed; the centroid
     # norms come from the fp32 centroids
-    qr = _bf16_round(q).astype(np.float64)
-    cr = _bf16_round(cent).astype(np.float64)
+    qr = bf16_round(q).astype(np.float64)
+    cr = bf16_round(cent).astype(np.float64)
     cn = (cent.astype(np.float64) ** 2).sum(axis=1)
     dot = qr @ cr.T
     absdot = np.abs(qr) @ np.abs(cr).T

@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
@@ -33,7 +34,18 @@ from distributed_faiss_amd.hip_engine import (  # noqa: E402
     HipProvider,
     merge_topk_dev,
 )
+from gpu_support import (  # noqa: E402
+    assert_lists_equal,
+    bf16_round,
+    codeword_rows,
+    decode_rows,
+    engine_with,
+    ivf_spec,
+    labels,
+    queries,
+)
 from oracle import (  # noqa: E402
+    from_engine_artifacts,
     kmeans,
     make_oracle_engine,
     partial_shuffle_indices,
@@ -57,8 +69,7 @@ K_REG, K_LDS = 10, 40  # register selection / LDS selection
 
 
 def _labels(rng):
-    lbl = np.repeat(np.arange(NLIST), LIST_SIZES)
-    rng.shuffle(lbl)
+    lbl = labels(rng, LIST_SIZES)
     assert lbl.shape[0] == NROWS
     return lbl
 
@@ -68,69 +79,26 @@ def _centroids(rng, d, spread):
 
 
 def _queries(rng, cent, d, metric):
-    """cent[l] + 0.7 N(0,1). Under IP every other query is then made
-    orthogonal to all centroids: its bias q.c is ~0, so the low bits of
-    the scan's own sum reach the result instead of being rounded away
-    under a bias of magnitude |c|^2 (the other half keeps the bias)."""
-    q = (cent[rng.integers(0, NLIST, NQ)]
-         + 0.7 * rng.standard_normal((NQ, d)))
-    if metric == IP:
-        c64 = cent.astype(np.float64)
-        coef = np.linalg.lstsq(c64.T, q[::2].T, rcond=None)[0]
-        q[::2] -= (c64.T @ coef).T
-    return q.astype(np.float32)
+    return queries(rng, cent, NQ, metric)
 
 
 def _spec(typ, d, metric, **kw):
-    return dict({"type": typ, "dim": d, "metric": metric, "nlist": NLIST,
-                 "nprobe": NLIST, "seed": 1234}, **kw)
+    return ivf_spec(typ, d, metric, NLIST, **kw)
 
 
 def _engine(spec, xb, cent, cb=None, vmin=None, vdiff=None):
-    eng = HipEngine(spec=spec)
-    eng.set_trained(cent, cb, vmin, vdiff)
-    eng.add(xb[:700])
-    eng.add(xb[700:])
-    return eng
+    return engine_with(spec, cent, cb, vmin, vdiff, xb, split=700)
 
 
 def _oracle(spec, xb, cent, cb=None, vmin=None, vdiff=None):
-    orc = make_oracle_engine(spec)
-    orc.centroids = cent
-    if cb is not None:
-        orc.codebooks = cb
-    if vmin is not None:
-        orc.vmin, orc.vdiff = vmin, vdiff
-        orc.scale = (vdiff / np.float32(255.0)).astype(np.float32)
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, cent, cb, vmin, vdiff)
     orc.add(xb)
     orc.nprobe = NLIST
     return orc
 
 
-def _oracle_lists(orc):
-    """(off, ids, code bytes) of the oracle's inverted lists, CSR order."""
-    off = np.zeros(orc.nlist + 1, np.int64)
-    off[1:] = np.cumsum([len(i) for i in orc.list_ids])
-    ids = np.concatenate(orc.list_ids)
-    if hasattr(orc, "list_data"):
-        rows = [np.ascontiguousarray(a).view(np.uint8).reshape(
-            a.shape[0], 4 * orc.d) for a in orc.list_data]
-    else:
-        rows = orc.list_codes
-    return off, ids, np.concatenate(rows)
-
-
 def _assert_lists_equal(eng, orc, lbl):
-    off_o, ids_o, codes_o = _oracle_lists(orc)
-    # the oracle's own lists are the intended ones
-    np.testing.assert_array_equal(np.diff(off_o), LIST_SIZES)
-    np.testing.assert_array_equal(
-        ids_o, np.concatenate([np.flatnonzero(lbl == l) for l in range(NLIST)]))
-    off, ids, codes = eng.get_lists()
-    np.testing.assert_array_equal(off, off_o)
-    np.testing.assert_array_equal(ids, ids_o)
-    np.testing.assert_array_equal(codes[:, :codes_o.shape[1]], codes_o)
+    assert_lists_equal(eng, orc, LIST_SIZES, lbl)
 
 
 class _OracleResults:
@@ -216,23 +184,10 @@ def _pq_case(m, dsub, metric, f16):
     cent = _centroids(rng, d, 5.0 if f16 else 20.0)
     cb = rng.standard_normal((m, 256, dsub)).astype(np.float32)
     lbl = _labels(rng)
-    cw = np.empty((NROWS, m), np.int64)
-    for j in range(m):
-        c64 = cb[j].astype(np.float64)
-        gap = np.sqrt(((c64[:, None, :] - c64[None, :, :]) ** 2).sum(-1))
-        np.fill_diagonal(gap, np.inf)
-        iso = np.flatnonzero(gap.min(axis=1) > CODEWORD_GAP)
-        assert iso.size >= 64
-        cw[:, j] = rng.choice(iso, NROWS)
     # a quarter of each list repeats the codes of another row of that list:
     # exact distance ties in every mode, inside and across the top-k
-    for l in range(NLIST):
-        rows = np.flatnonzero(lbl == l)
-        if rows.size >= 4:
-            dup = rows[: rows.size // 4]
-            cw[dup] = cw[rng.choice(rows[rows.size // 4:], dup.size)]
-    dec = np.concatenate([cb[j][cw[:, j]] for j in range(m)], axis=1)
-    xb = (cent[lbl] + dec
+    cw = codeword_rows(rng, cb, lbl, CODEWORD_GAP, 64)
+    xb = (cent[lbl] + decode_rows(cb, cw)
           + 1e-3 * rng.standard_normal((NROWS, d))).astype(np.float32)
     q = _queries(rng, cent, d, metric)
     spec = _spec("ivfpq", d, metric, m=m, pq_lut_f16=1 if f16 else 0)
@@ -337,7 +292,7 @@ def _sq8_case(d, metric):
     vdiff = rng.uniform(2.0, 6.0, d).astype(np.float32)
     c = rng.integers(0, 256, (NROWS, d))
     jit = rng.uniform(-0.1, 0.1, (NROWS, d))
-    resid = vmin + (c + 0.5 + jit) * (vdiff.astype(np.float64) / 255.0)
+    resid = vmin + (c + 0.5 + jit) * (vdiff.astype(np.float64) / 255)
     # ~3 % of the entries leave the trained range by 0.5-2 x vdiff
     out = rng.uniform(0.0, 1.0, (NROWS, d))
     push = rng.uniform(0.5, 2.0, (NROWS, d)) * vdiff
@@ -509,14 +464,6 @@ def test_ivfflat_scan_dispatch_tolerance(d, metric):
 # ---------------------------------------------------------------------------
 
 
-def _bf16_round(a):
-    """k_f32_to_bf16's integer formula: (u + 0x7FFF + lsb) >> 16."""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    lsb = (u >> np.uint64(16)) & np.uint64(1)
-    r = ((u + np.uint64(0x7FFF) + lsb) >> np.uint64(16)) & np.uint64(0xFFFF)
-    return (r << np.uint64(16)).astype(np.uint32).view(np.float32)
-
-
 def _check_coarse(nq, nlist, d, metric, nprobe, bf16):
     rng = np.random.default_rng(nq * 7919 + nlist * 31 + d)
     cent = rng.standard_normal((nlist, d)).astype(np.float32)
@@ -529,8 +476,8 @@ def _check_coarse(nq, nlist, d, metric, nprobe, bf16):
     assert probes.shape == (nq, nprobe)
     # fp64 reference over the operands the GEMM consumed; the centroid
     # norms come from the fp32 centroids in both modes
-    qr = (_bf16_round(q) if bf16 else q).astype(np.float64)
-    cr = (_bf16_round(cent) if bf16 else cent).astype(np.float64)
+    qr = (bf16_round(q) if bf16 else q).astype(np.float64)
+    cr = (bf16_round(cent) if bf16 else cent).astype(np.float64)
     cn = (cent.astype(np.float64) ** 2).sum(axis=1)
     dot = qr @ cr.T
     absdot = np.abs(qr) @ np.abs(cr).T

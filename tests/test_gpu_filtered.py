@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
@@ -29,7 +30,12 @@ if not torch.cuda.is_available():
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
 from distributed_faiss_amd.index import Index  # noqa: E402
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
-from oracle import make_oracle_engine  # noqa: E402
+from gpu_support import (  # noqa: E402
+    clustered as _clustered,
+    rand as _rand,
+    wait_trained as _wait_trained,
+)
+from oracle import from_engine_artifacts, make_oracle_engine  # noqa: E402
 
 IP, L2 = 0, 1
 FLT_MAX = np.float32(3.4028235e38)
@@ -37,18 +43,6 @@ NTOTAL = 3187
 D_, NLIST = 32, 8
 FILTERS = ["ALL", "NONE", "MOD3", "SPARSE", "NOLIST"]
 CFGS = [("ivfpq", None), ("ivfsq", "8bit"), ("ivfsq", "fp16")]
-
-
-def _rand(n, d, seed=0):
-    return np.random.default_rng(seed).standard_normal((n, d), dtype=np.float32)
-
-
-def _clustered(nlist, per, d, seed=0, sep=20.0, sigma=0.05):
-    rng = np.random.default_rng(seed)
-    cent = rng.standard_normal((nlist, d)).astype(np.float32) * sep
-    lbl = rng.integers(0, nlist, nlist * per)
-    x = cent[lbl] + sigma * rng.standard_normal((nlist * per, d)).astype(np.float32)
-    return cent, x.astype(np.float32)
 
 
 def _pad(metric):
@@ -92,14 +86,8 @@ def _engine(spec, art, batches):
 
 
 def _oracle(spec, art, xb):
-    orc = make_oracle_engine(spec)
-    orc.centroids = art["cent"]
-    if "codebooks" in art:
-        orc.codebooks = art["codebooks"]
-    if "vmin" in art:
-        orc.vmin, orc.vdiff = art["vmin"], art["vdiff"]
-        orc.scale = (art["vdiff"] / np.float32(255.0)).astype(np.float32)
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, art["cent"], art.get("codebooks"),
+                                art.get("vmin"), art.get("vdiff"))
     orc.add(xb)
     orc.nprobe = spec["nlist"]
     return orc
@@ -406,19 +394,6 @@ def test_hnswsq_is_unsupported():
 # ---------------------------------------------------------------------------
 # Index.search_filtered through the product provider
 # ---------------------------------------------------------------------------
-
-
-def _wait_trained(idx):
-    import time
-
-    from distributed_faiss_amd.index_state import IndexState
-
-    t0 = time.time()
-    while time.time() - t0 < 30:
-        if idx.get_state() == IndexState.TRAINED:
-            return
-        time.sleep(0.01)
-    raise AssertionError("index did not reach TRAINED")
 
 
 def test_index_search_filtered_hip_provider(tmp_path):

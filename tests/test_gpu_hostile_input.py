@@ -43,12 +43,12 @@ torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
-import range_ref  # noqa: E402
-from pq4_ref import OraclePQ4  # noqa: E402
-from sq_bits_ref import OracleSQBits  # noqa: E402
-
 from distributed_faiss_amd.hip_engine import HipEngine  # noqa: E402
-from oracle import make_oracle_engine  # noqa: E402
+from oracle import (  # noqa: E402
+    from_engine_artifacts,
+    range_from_scans,
+    scan_lists,
+)
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -237,39 +237,11 @@ def _engine(c, **knobs):
 
 def _oracle(c, eng):
     """Oracle of an exact-tier case over the ENGINE's inverted lists."""
-    if "orc" in c:
-        return c["orc"]
-    spec, metric, d = c["spec"], c["metric"], c["d"]
-    off, ids, codes = eng.get_lists()
-    sq = spec.get("sq_type")
-    if c["typ"] == "ivfpq" and spec.get("nbits", 8) == 4:
-        orc = OraclePQ4(d, NLIST, spec["m"], metric)
-        orc.centroids, orc.codebooks = c["cent"], c["cb"]
-        orc.load_lists(off, ids, codes)
-    elif sq in ("6bit", "4bit"):
-        orc = OracleSQBits(d, NLIST, metric, int(sq[0]))
-        orc.centroids = c["cent"]
-        orc.set_ranges(c["vmin"], c["vdiff"])
-        orc.load_lists(off, ids, codes)
-    else:
-        ospec = {k: v for k, v in spec.items()
-                 if k not in ("opq", "refine", "k_factor")}
-        orc = make_oracle_engine(ospec)
-        orc.centroids = c["cent"]
-        if c["cb"] is not None:
-            orc.codebooks = c["cb"]
-        if sq == "8bit":
-            orc.vmin, orc.vdiff = c["vmin"], c["vdiff"]
-            orc.scale = (c["vdiff"] / np.float32(255.0)).astype(np.float32)
-        nb = orc.list_codes[0].shape[1]
-        orc.list_ids = [ids[off[l]:off[l + 1]].astype(np.int64)
-                        for l in range(NLIST)]
-        orc.list_codes = [np.ascontiguousarray(codes[off[l]:off[l + 1], :nb])
-                          for l in range(NLIST)]
-        orc.ntotal = int(off[-1])
-    orc.is_trained = True
-    c["orc"] = orc
-    return orc
+    if "orc" not in c:
+        c["orc"] = from_engine_artifacts(
+            c["spec"], c["cent"], c["cb"], c["vmin"], c["vdiff"],
+            lists=eng.get_lists())
+    return c["orc"]
 
 
 def _oracle_q(c, eng, q):
@@ -287,7 +259,7 @@ def _scans(c, eng, q, probes, keys, rows):
     for i in rows:
         slots = [s for s in range(probes.shape[1])
                  if 0 <= int(probes[i, s]) < NLIST]
-        out[i] = range_ref.scan_lists(
+        out[i] = scan_lists(
             orc, qo[i:i + 1], probes[i:i + 1, slots], keys[i:i + 1, slots])[0]
     return out
 
@@ -452,7 +424,7 @@ def test_nonfinite_queries_every_entry(kind, metric, k):
                 _same(Drb[lb[i]:lb[i + 1]], Drz[lz[i]:lz[i + 1]], "range D")
                 _same(Irb[lb[i]:lb[i + 1]], Irz[lz[i]:lz[i + 1]], "range I")
                 if tier == "exact":
-                    _, Dr, Ir = range_ref.range_from_scans(
+                    _, Dr, Ir = range_from_scans(
                         [scans[i]], metric, radius)
                     _same(Drb[lb[i]:lb[i + 1]], Dr, "range oracle D")
                     _same(Irb[lb[i]:lb[i + 1]], Ir, "range oracle I")
@@ -545,7 +517,7 @@ def test_invalid_probes_are_empty_slots(kind, metric):
                 if name == "query2":
                     assert lg[3] == lg[2], what
                 if exact:
-                    lr, Dr, Ir = range_ref.range_from_scans(
+                    lr, Dr, Ir = range_from_scans(
                         [scans[i] for i in range(NQ)], metric, r, allow)
                     _same(lg, lr, what + " oracle lims")
                     _same(Dg, Dr, what + " oracle D")

@@ -17,16 +17,21 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
-from distributed_faiss_amd.hip_engine import (  # noqa: E402
-    HipEngine,
-    merge_topk_dev,
+from distributed_faiss_amd.hip_engine import merge_topk_dev  # noqa: E402
+from gpu_support import (  # noqa: E402
+    assert_bitwise,
+    codeword_rows,
+    decode_rows,
+    engine_with,
+    labels,
 )
-from oracle import make_oracle_engine  # noqa: E402
+from oracle import from_engine_artifacts  # noqa: E402
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -46,11 +51,6 @@ def _both(run):
         if saved is not None:
             os.environ[KNOB] = saved
     return wave, block
-
-
-def _assert_bitwise_equal(a, b):
-    np.testing.assert_array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
-    np.testing.assert_array_equal(a[1], b[1])
 
 
 # ---------------------------------------------------------------------------
@@ -94,7 +94,7 @@ def test_shard_merge_wave_vs_block_vs_lexsort(S, k, nq, maximize):
         return Dm.cpu().numpy(), Im.cpu().numpy()
 
     wave, block = _both(run)
-    _assert_bitwise_equal(wave, block)
+    assert_bitwise(*wave, *block)
     Dm, Im = wave
     # key = -v for maximize (kept in the output: reference quirk 2);
     # order by (key, dense slot s*k + j); id = s*nq*k + q*k + j
@@ -123,8 +123,7 @@ assert NLIST == 32 and NROWS == 1992
 def _data(typ, metric):
     """(spec, cent, cb, xb, q, lbl, cw): numpy only."""
     rng = np.random.default_rng(77 + metric)
-    lbl = np.repeat(np.arange(NLIST), LIST_SIZES)
-    rng.shuffle(lbl)
+    lbl = labels(rng, LIST_SIZES)
     if typ == "ivf_flat":
         # small integers: every product and partial sum is exact in fp32,
         # so the engine's tree reduction and the oracle's sequential sum
@@ -145,21 +144,8 @@ def _data(typ, metric):
         d = m * dsub
         cent = (rng.standard_normal((NLIST, d)) * 20.0).astype(np.float32)
         cb = rng.standard_normal((m, 256, dsub)).astype(np.float32)
-        cw = np.empty((NROWS, m), np.int64)
-        for j in range(m):
-            c64 = cb[j].astype(np.float64)
-            gap = np.sqrt(((c64[:, None, :] - c64[None, :, :]) ** 2).sum(-1))
-            np.fill_diagonal(gap, np.inf)
-            iso = np.flatnonzero(gap.min(axis=1) > 0.05)
-            assert iso.size >= 64
-            cw[:, j] = rng.choice(iso, NROWS)
-        for l in range(NLIST):
-            rows = np.flatnonzero(lbl == l)
-            if rows.size >= 4:
-                dup = rows[: rows.size // 4]
-                cw[dup] = cw[rng.choice(rows[rows.size // 4:], dup.size)]
-        dec = np.concatenate([cb[j][cw[:, j]] for j in range(m)], axis=1)
-        xb = (cent[lbl] + dec
+        cw = codeword_rows(rng, cb, lbl, 0.05, 64)
+        xb = (cent[lbl] + decode_rows(cb, cw)
               + 1e-3 * rng.standard_normal((NROWS, d))).astype(np.float32)
         q = (cent[rng.integers(0, NLIST, NQ)]
              + 0.7 * rng.standard_normal((NQ, d))).astype(np.float32)
@@ -171,15 +157,8 @@ def _data(typ, metric):
 def _build(typ, metric):
     """Engine and oracle over the same set_trained artifacts."""
     spec, cent, cb, xb, q, lbl, cw = _data(typ, metric)
-    eng = HipEngine(spec=spec)
-    eng.set_trained(cent, cb)
-    eng.add(xb[:1000])
-    eng.add(xb[1000:])
-    orc = make_oracle_engine(spec)
-    orc.centroids = cent
-    if cb is not None:
-        orc.codebooks = cb
-    orc.is_trained = True
+    eng = engine_with(spec, cent, cb, xb=xb, split=1000)
+    orc = from_engine_artifacts(spec, cent, cb)
     orc.add(xb)
     # both hold the intended lists
     np.testing.assert_array_equal([len(i) for i in orc.list_ids], LIST_SIZES)
@@ -208,7 +187,7 @@ def _check(c, probes, keys, k):
     """wave == block bitwise, wave == oracle; returns the wave (D, I)."""
     wave, block = _both(
         lambda: c["eng"].search_preassigned(c["q"], probes, keys, k))
-    _assert_bitwise_equal(wave, block)
+    assert_bitwise(*wave, *block)
     Do, Io = c["orc"].search_preassigned(c["q"], probes, keys, k)
     np.testing.assert_array_equal(wave[1], Io)
     np.testing.assert_array_equal(wave[0], Do)  # BITWISE

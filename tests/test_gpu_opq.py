@@ -1,5 +1,5 @@
 # OPQ pre-transform (spec "opq": 1) on the GPU, against the
-# numpy restatement tests/opq_ref.py.
+# numpy restatement oracle/opq.py.
 #
 #  1. bit-exact tier: A a signed permutation / selection (y = A x exact in any
 #     summation order), artifacts injected — search_preassigned and the
@@ -7,7 +7,7 @@
 #     ivfpq engine at d_out fed the permuted data;
 #  2. equivalence on a general rotation: the OPQ engine is bitwise the plain
 #     d_out engine behind apply_transform — plain, filtered, preassigned and
-#     with refine on top (tests/refine_ref.py over the ORIGINAL vectors);
+#     with refine on top (oracle/refine.py over the ORIGINAL vectors);
 #  3. transform values in the project's tolerance tier, independent of the
 #     batch shape; reconstruct = A^T . decode;
 #  4. training: orthonormal rows, quantization error, determinism, a
@@ -37,8 +37,17 @@ if not torch.cuda.is_available():
 
 from distributed_faiss_amd import Index, IndexCfg  # noqa: E402
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
-import opq_ref  # noqa: E402
-from refine_ref import k_prime, refine_ref  # noqa: E402
+from gpu_support import (  # noqa: E402
+    assert_bitwise as _bitwise,
+    assert_lists_equal,
+    labels,
+    wait_trained as _wait_trained,
+)
+from oracle import opq  # noqa: E402
+from oracle.refine import (  # noqa: E402
+    k_prime,
+    refine_ref,
+)
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -70,12 +79,6 @@ def _plain_spec(d_out, m, metric, nbits, **kw):
                  "nbits": nbits}, **kw)
 
 
-def _bitwise(D, I, Dr, Ir):
-    np.testing.assert_array_equal(I, Ir)
-    np.testing.assert_array_equal(np.asarray(D).view(np.uint32),
-                                  np.asarray(Dr).view(np.uint32))
-
-
 def _lift(A, y, rng):
     """x (n, d_in) float32 with A x == y exactly, for a signed selection A:
     the selected coordinates carry +-y, the others anything."""
@@ -99,11 +102,10 @@ def _exact_case(d_in, d_out, m, metric, nbits):
     ksub = 1 << nbits
     dsub = d_out // m
     rng = np.random.default_rng(7000 + 100 * d_in + d_out + nbits + metric)
-    A = opq_ref.signed_selection(d_in, d_out, rng)
+    A = opq.signed_selection(d_in, d_out, rng)
     cent = (rng.standard_normal((NLIST, d_out)) * 20.0).astype(np.float32)
     cb = rng.standard_normal((m, ksub, dsub)).astype(np.float32)
-    lbl = np.repeat(np.arange(NLIST), LIST_SIZES)
-    rng.shuffle(lbl)
+    lbl = labels(rng, LIST_SIZES)
     cw = np.empty((NROWS, m), np.int64)
     for j in range(m):
         c64 = cb[j].astype(np.float64)
@@ -118,25 +120,20 @@ def _exact_case(d_in, d_out, m, metric, nbits):
     yq = (cent[rng.integers(0, NLIST, NQ)]
           + 0.7 * rng.standard_normal((NQ, d_out))).astype(np.float32)
     xb, q = _lift(A, yb, rng), _lift(A, yq, rng)
-    orc = opq_ref.OracleOPQ(A, NLIST, m, metric, nbits)
+    orc = opq.OracleOPQ(A, NLIST, m, metric, nbits)
     orc.set_trained(cent, cb)
     # the transform is exact on this construction
     np.testing.assert_array_equal(orc.apply(xb), yb)
     np.testing.assert_array_equal(orc.apply(q), yq)
     orc.add(xb[:SPLIT])
     orc.add(xb[SPLIT:])
-    off, ids, codes = orc.lists()
-    np.testing.assert_array_equal(np.diff(off), LIST_SIZES)
+    np.testing.assert_array_equal(np.diff(orc.lists()[0]), LIST_SIZES)
     return {"A": A, "cent": cent, "cb": cb, "xb": xb, "q": q, "yb": yb,
-            "yq": yq, "orc": orc, "lists": (off, ids, codes), "res": {}}
+            "yq": yq, "orc": orc, "res": {}}
 
 
 def _assert_lists(eng, case):
-    off_o, ids_o, codes_o = case["lists"]
-    off, ids, codes = eng.get_lists()
-    np.testing.assert_array_equal(off, off_o)
-    np.testing.assert_array_equal(ids, ids_o)
-    np.testing.assert_array_equal(codes[:, :codes_o.shape[1]], codes_o)
+    assert_lists_equal(eng, case["orc"].inner, LIST_SIZES)
 
 
 @pytest.mark.parametrize("nbits", NBITS)
@@ -179,7 +176,7 @@ def test_signed_permutation_bitexact(d_in, d_out, m, metric, nbits):
 def _rot_case(d_in, d_out, m, metric, nbits):
     ksub = 1 << nbits
     rng = np.random.default_rng(9000 + 100 * d_in + d_out + nbits + metric)
-    A = opq_ref.random_rotation(d_in, d_out, rng)
+    A = opq.random_rotation(d_in, d_out, rng)
     cent = (rng.standard_normal((NLIST, d_out)) * 2.0).astype(np.float32)
     cb = (0.5 * rng.standard_normal((m, ksub, d_out // m))).astype(np.float32)
     # rows around the centroids pulled back to d_in, plus an off-subspace
@@ -297,8 +294,8 @@ def test_apply_transform_values_and_batch_independence(d_in, d_out, m):
     q = c["q"]
     y = eng.apply_transform(q)
     assert y.shape == (NQ, d_out) and y.dtype == np.float32
-    err = np.abs(y.astype(np.float64) - opq_ref.transform64(c["A"], q))
-    assert (err <= opq_ref.transform_bound(c["A"], q)).all(), err.max()
+    err = np.abs(y.astype(np.float64) - opq.transform64(c["A"], q))
+    assert (err <= opq.transform_bound(c["A"], q)).all(), err.max()
     # one 130-row call == 130 one-row calls == rows inside another batch
     rows = np.concatenate([eng.apply_transform(q[i:i + 1]) for i in range(NQ)])
     np.testing.assert_array_equal(rows.view(np.uint32), y.view(np.uint32))
@@ -359,7 +356,7 @@ def _train(zero_col=None, d_out=32):
     if d_out != 32:
         spec["opq_dim"] = d_out
     eng = HipEngine(spec=spec)
-    eng.train(opq_ref.recipe(zero_col))
+    eng.train(opq.recipe(zero_col))
     assert eng.is_trained
     return eng, eng.get_transform()
 
@@ -368,13 +365,13 @@ def _train(zero_col=None, d_out=32):
 def _ref_dev(zero_col=None, d_out=32, niter=2):
     """max|A A^T - I| of the SVD-polar reference rotation after its single
     rounding to float32 (the figure does not depend on niter)."""
-    A = opq_ref.opq_train(opq_ref.recipe(zero_col), 8, 16, d_out=d_out,
+    A = opq.opq_train(opq.recipe(zero_col), 8, 16, d_out=d_out,
                           niter=niter)
-    return opq_ref.ortho_dev(A.astype(np.float32))
+    return opq.ortho_dev(A.astype(np.float32))
 
 
 def _check_orthonormal(A, x, ref_dev):
-    dev = opq_ref.ortho_dev(A)
+    dev = opq.ortho_dev(A)
     print(f"max|AA^T - I|: engine {dev:.3e}, fp32-rounded reference "
           f"{ref_dev:.3e}")
     # x 8: iteration round-off against a single rounding
@@ -389,16 +386,16 @@ def _check_orthonormal(A, x, ref_dev):
 def test_trained_rows_are_orthonormal():
     _eng, A = _train()
     assert A.shape == (32, 32) and A.dtype == np.float32
-    _check_orthonormal(A, opq_ref.recipe(), _ref_dev(niter=8))
+    _check_orthonormal(A, opq.recipe(), _ref_dev(niter=8))
 
 
 def test_trained_rotation_halves_the_quantization_error():
     _eng, A = _train()
-    xc = opq_ref.centred(opq_ref.recipe())
-    plain = opq_ref.pq_mse(xc, 8, 16)
-    rot = opq_ref.pq_mse(opq_ref.transform(A, xc), 8, 16)
-    Aref = opq_ref.opq_train(opq_ref.recipe(), 8, 16, niter=8)
-    ref = opq_ref.pq_mse(opq_ref.transform(Aref.astype(np.float32), xc), 8, 16)
+    xc = opq.centred(opq.recipe())
+    plain = opq.pq_mse(xc, 8, 16)
+    rot = opq.pq_mse(opq.transform(A, xc), 8, 16)
+    Aref = opq.opq_train(opq.recipe(), 8, 16, niter=8)
+    ref = opq.pq_mse(opq.transform(Aref.astype(np.float32), xc), 8, 16)
     print(f"PQ mse: plain {plain:.2f}, engine OPQ {rot:.2f} "
           f"({rot / plain:.3f}), reference OPQ {ref:.2f} ({ref / plain:.3f})")
     assert rot <= 0.5 * plain
@@ -407,7 +404,7 @@ def test_trained_rotation_halves_the_quantization_error():
 def test_training_is_deterministic():
     _eng, A = _train()
     eng2 = HipEngine(spec=dict(TRAIN_KW))
-    eng2.train(opq_ref.recipe())
+    eng2.train(opq.recipe())
     np.testing.assert_array_equal(eng2.get_transform().view(np.uint32),
                                   A.view(np.uint32))
     # the inner index was trained on the transformed rows, equally
@@ -416,7 +413,7 @@ def test_training_is_deterministic():
 
 
 def test_training_on_rank_deficient_rows():
-    x = opq_ref.recipe(zero_col=5)
+    x = opq.recipe(zero_col=5)
     assert not x[:, 5].any()
     _eng, A = _train(zero_col=5)
     _check_orthonormal(A, x, _ref_dev(zero_col=5))
@@ -426,14 +423,14 @@ def test_training_with_reduced_dim():
     eng, A = _train(d_out=16)
     assert A.shape == (16, 32)
     assert eng.transform_info() == (1, 32, 16)
-    _check_orthonormal(A, opq_ref.recipe(), _ref_dev(d_out=16))
+    _check_orthonormal(A, opq.recipe(), _ref_dev(d_out=16))
     assert eng.get_centroids().shape == (NLIST, 16)
     assert eng.get_codebooks().shape == (8, 16, 2)
 
 
 def test_trained_index_searches_like_plain_behind_apply():
     eng, _A = _train()
-    x = opq_ref.recipe()[:1500]
+    x = opq.recipe()[:1500]
     if eng.ntotal == 0:
         eng.add(x)
     plain = HipEngine(spec={k: v for k, v in TRAIN_KW.items()
@@ -533,20 +530,6 @@ def test_surface_and_errors():
             HipEngine(spec=dict(_spec(40, 24, 8, L2, 8), **bad))
 
 
-def _wait_trained(idx, ntotal):
-    import time
-
-    from distributed_faiss_amd.index_state import IndexState
-
-    t0 = time.time()
-    while time.time() - t0 < 30:
-        if (idx.get_state() == IndexState.TRAINED
-                and idx.engine.ntotal == ntotal):
-            return
-        time.sleep(0.01)
-    raise AssertionError("index did not reach TRAINED")
-
-
 def _clustered(seed, n=1500, d=32):
     rng = np.random.default_rng(seed)
     cent = 4.0 * rng.standard_normal((NLIST, d))
@@ -571,7 +554,7 @@ def test_index_end_to_end(tmp_path, factory, info, refine):
     _wait_trained(idx, n)
     eng = idx.engine
     assert eng.transform_info() == info and eng.d == 32
-    assert opq_ref.ortho_dev(eng.get_transform()) < 1e-5
+    assert opq.ortho_dev(eng.get_transform()) < 1e-5
     assert idx.get_centroids().shape == (NLIST, info[2])
     scores, ids, metas, _ = idx.search_full(q, 10)
     assert [[m[2] for m in row] for row in metas] == ids.tolist()

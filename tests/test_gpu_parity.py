@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
@@ -27,22 +28,10 @@ from distributed_faiss_amd.hip_engine import (  # noqa: E402
     HipProvider,
     merge_topk_dev,
 )
-from oracle import make_oracle_engine  # noqa: E402
+from gpu_support import clustered as _clustered, rand as _rand  # noqa: E402
+from oracle import from_engine_artifacts, make_oracle_engine  # noqa: E402
 
 IP, L2 = 0, 1
-
-
-def _rand(n, d, seed=0):
-    return np.random.default_rng(seed).standard_normal((n, d), dtype=np.float32)
-
-
-def _clustered(nlist, per, d, seed=0, sep=20.0, sigma=0.05):
-    """Well-separated clusters: assignment unambiguous for engine & oracle."""
-    rng = np.random.default_rng(seed)
-    cent = rng.standard_normal((nlist, d)).astype(np.float32) * sep
-    lbl = rng.integers(0, nlist, nlist * per)
-    x = cent[lbl] + sigma * rng.standard_normal((nlist * per, d)).astype(np.float32)
-    return cent, x.astype(np.float32)
 
 
 # ---------------------------------------------------------------------------
@@ -117,15 +106,11 @@ def test_tie_break_ascending_ids():
 
 
 def _mk_oracle_with_engine_artifacts(eng, spec, xb):
-    orc = make_oracle_engine(spec)
-    orc.centroids = eng.get_centroids()
-    if spec["type"] == "ivfpq":
-        orc.codebooks = eng.get_codebooks()
+    cb = eng.get_codebooks() if spec["type"] == "ivfpq" else None
+    vmin = vdiff = None
     if spec["type"] == "ivfsq" and spec.get("sq_type") == "8bit":
         vmin, vdiff = eng.get_sq_params()
-        orc.vmin, orc.vdiff = vmin, vdiff
-        orc.scale = (vdiff / np.float32(255.0)).astype(np.float32)
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, eng.get_centroids(), cb, vmin, vdiff)
     orc.add(xb)
     orc.nprobe = spec["nprobe"]
     return orc
@@ -190,15 +175,8 @@ def _bitexact_setup(typ, metric, sq_type=None, d=32, nlist=8, per=400):
     eng.set_trained(cent, kwargs.get("codebooks"), kwargs.get("vmin"),
                     kwargs.get("vdiff"))
     eng.add(xb)
-    orc = make_oracle_engine(spec)
-    orc.centroids = cent
-    if "codebooks" in kwargs:
-        orc.codebooks = kwargs["codebooks"]
-    if "vmin" in kwargs:
-        orc.vmin = kwargs["vmin"]
-        orc.vdiff = kwargs["vdiff"]
-        orc.scale = (kwargs["vdiff"] / np.float32(255.0)).astype(np.float32)
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, cent, kwargs.get("codebooks"),
+                                kwargs.get("vmin"), kwargs.get("vdiff"))
     orc.add(xb)
     orc.nprobe = nlist
     q = xb[::37][:20] + 0.01 * rng.standard_normal((20, d)).astype(np.float32)
@@ -229,9 +207,7 @@ def test_ivfflat_tolerance_parity():
     eng = HipEngine(spec=spec)
     eng.set_trained(cent)
     eng.add(xb)
-    orc = make_oracle_engine(spec)
-    orc.centroids = cent
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, cent)
     orc.add(xb)
     orc.nprobe = nlist
     q = xb[:15] + 0.01 * _rand(15, d, 13)
@@ -377,8 +353,7 @@ def test_pq_glut_path_bitexact(m, metric):
     np.testing.assert_array_equal(D1, D2)  # BITWISE across chunk sizes
     spec_o = {"type": "ivfpq", "dim": d, "metric": metric, "nlist": nlist,
               "m": m, "nprobe": nlist, "seed": 7}
-    orc = make_oracle_engine(spec_o)
-    orc.centroids, orc.codebooks, orc.is_trained = cent, cb, True
+    orc = from_engine_artifacts(spec_o, cent, cb)
     orc.add(xb)
     orc.nprobe = nlist
     eng = HipEngine(spec=dict(spec_o, pq_lut_global=1))

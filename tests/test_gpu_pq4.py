@@ -1,10 +1,11 @@
 # 4-bit product quantization (spec "nbits": 4) on the GPU,
-# against the numpy restatement tests/pq4_ref.py.
+# against the CPU oracle (oracle.OracleIVFPQ at nbits=4).
 #
 #  * bit-exact tier (assert_array_equal on D and I, byte equality of the
 #    packed inverted lists): plain, filtered, reconstruct, refine on top,
 #    save/load — on the construction of tests/test_gpu_dispatch_parity.py
-#    (helpers copied), each shape named by the dispatch point it pins;
+#    (helpers in tests/gpu_support.py), each shape named by the dispatch
+#    point it pins;
 #  * training against oracle.kmeans with 16 codewords per subspace;
 #  * end to end on Gaussian data: the encode in its tolerance tier, the
 #    scan bitwise on the engine's own lists;
@@ -27,9 +28,24 @@ if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
-from oracle import kmeans, partial_shuffle_indices  # noqa: E402
-from pq4_ref import KSUB, OraclePQ4, unpack  # noqa: E402
-from refine_ref import refine_ref  # noqa: E402
+from gpu_support import (  # noqa: E402
+    assert_lists_equal,
+    codeword_rows,
+    decode_rows,
+    engine_with,
+    ivf_spec,
+    labels,
+    queries,
+)
+from oracle import (  # noqa: E402
+    from_engine_artifacts,
+    kmeans,
+    partial_shuffle_indices,
+    unpack_pq4,
+)
+from oracle.refine import (  # noqa: E402
+    refine_ref,
+)
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -45,40 +61,16 @@ NLIST = len(LIST_SIZES)
 NROWS = sum(LIST_SIZES)  # 1231
 NQ = 8
 K_REG, K_LDS = 10, 40  # register selection / LDS selection
+KSUB = 16
 CODEWORD_GAP = 0.05  # data uses codewords at least this far from any other
 
 
-def _labels(rng):
-    lbl = np.repeat(np.arange(NLIST), LIST_SIZES)
-    rng.shuffle(lbl)
-    assert lbl.shape[0] == NROWS
-    return lbl
-
-
-def _queries(rng, cent, d, metric):
-    """cent[l] + 0.7 N(0,1). Under IP every other query is then made
-    orthogonal to all centroids: its bias q.c is ~0, so the low bits of
-    the scan's own sum reach the result instead of being rounded away."""
-    q = (cent[rng.integers(0, NLIST, NQ)]
-         + 0.7 * rng.standard_normal((NQ, d)))
-    if metric == IP:
-        c64 = cent.astype(np.float64)
-        coef = np.linalg.lstsq(c64.T, q[::2].T, rcond=None)[0]
-        q[::2] -= (c64.T @ coef).T
-    return q.astype(np.float32)
-
-
 def _spec(d, metric, m, **kw):
-    return dict({"type": "ivfpq", "dim": d, "metric": metric, "nlist": NLIST,
-                 "nprobe": NLIST, "seed": 1234, "m": m, "nbits": 4}, **kw)
+    return ivf_spec("ivfpq", d, metric, NLIST, m=m, **dict({"nbits": 4}, **kw))
 
 
 def _engine(spec, case):
-    eng = HipEngine(spec=spec)
-    eng.set_trained(case["cent"], case["cb"])
-    eng.add(case["xb"][:700])
-    eng.add(case["xb"][700:])
-    return eng
+    return engine_with(spec, case["cent"], case["cb"], xb=case["xb"], split=700)
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,30 +83,16 @@ def _case(m, dsub, metric):
     rng = np.random.default_rng(4000 + 1000 * m + dsub)
     cent = (rng.standard_normal((NLIST, d)) * 20.0).astype(np.float32)
     cb = rng.standard_normal((m, KSUB, dsub)).astype(np.float32)
-    lbl = _labels(rng)
-    cw = np.empty((NROWS, m), np.int64)
-    for j in range(m):
-        c64 = cb[j].astype(np.float64)
-        gap = np.sqrt(((c64[:, None, :] - c64[None, :, :]) ** 2).sum(-1))
-        np.fill_diagonal(gap, np.inf)
-        iso = np.flatnonzero(gap.min(axis=1) > CODEWORD_GAP)
-        assert iso.size >= 8
-        cw[:, j] = rng.choice(iso, NROWS)
+    lbl = labels(rng, LIST_SIZES)
+    assert lbl.shape[0] == NROWS
     # a quarter of each list repeats the codes of another row of that list:
     # exact distance ties, inside and across the top-k
-    for l in range(NLIST):
-        rows = np.flatnonzero(lbl == l)
-        if rows.size >= 4:
-            dup = rows[: rows.size // 4]
-            cw[dup] = cw[rng.choice(rows[rows.size // 4:], dup.size)]
-    dec = np.concatenate([cb[j][cw[:, j]] for j in range(m)], axis=1)
-    xb = (cent[lbl] + dec
+    cw = codeword_rows(rng, cb, lbl, CODEWORD_GAP, 8)
+    xb = (cent[lbl] + decode_rows(cb, cw)
           + 1e-3 * rng.standard_normal((NROWS, d))).astype(np.float32)
-    q = _queries(rng, cent, d, metric)
-    orc = OraclePQ4(d, NLIST, m, metric)
-    orc.centroids, orc.codebooks, orc.is_trained = cent, cb, True
+    q = queries(rng, cent, NQ, metric)
+    orc = from_engine_artifacts(_spec(d, metric, m), cent, cb)
     orc.add(xb)
-    orc.nprobe = NLIST
     # CPU conditions: the restatement encoded the intended codewords, its
     # lists are the intended ones, and every nibble value occurs in both
     # the low and the high position
@@ -155,14 +133,10 @@ def _coarse(eng, case):
 
 
 def _assert_lists_equal(eng, case):
-    off_o, ids_o, packed_o = case["orc"].packed_lists()
-    off, ids, codes = eng.get_lists()
+    codes = assert_lists_equal(eng, case["orc"])
     m = case["m"]
     assert codes.shape[1] == (((m + 1) // 2 + 15) // 16) * 16  # ceil16
-    np.testing.assert_array_equal(off, off_o)
-    np.testing.assert_array_equal(ids, ids_o)
-    assert packed_o.shape[1] == (m + 1) // 2
-    np.testing.assert_array_equal(codes[:, :packed_o.shape[1]], packed_o)
+    assert case["orc"].packed_lists()[2].shape[1] == (m + 1) // 2
     if m % 2:  # the unused high nibble of the last code byte
         assert (codes[:, m // 2] >> 4 == 0).all()
 
@@ -419,7 +393,7 @@ def test_end_to_end_gaussian(metric):
     assert cb.shape == (m, KSUB, dsub)
     off, ids, packed = eng.get_lists()
     assert off[-1] == n and np.array_equal(np.sort(ids), np.arange(n))
-    codes = unpack(packed, m)
+    codes = unpack_pq4(packed, m)
     assert codes.max() < KSUB and np.unique(codes).size == KSUB
     # encode tolerance tier: the stored codeword is a nearest one in fp64
     lst = np.repeat(np.arange(nlist), np.diff(off))
@@ -433,9 +407,7 @@ def test_end_to_end_gaussian(metric):
             + 1e-4
         assert (got <= dist.min(axis=1) + tol).all(), j
     # scan: the restatement on the engine's own artifacts, bitwise
-    orc = OraclePQ4(d, nlist, m, metric)
-    orc.centroids, orc.codebooks, orc.is_trained = cent, cb, True
-    orc.load_lists(off, ids, packed)
+    orc = from_engine_artifacts(spec, cent, cb, lists=(off, ids, packed))
     probes, keys = eng.coarse(q, nlist)
     Do, Io = orc.search_preassigned(q, probes, keys, K_LDS)
     for k in (K_REG, K_LDS):

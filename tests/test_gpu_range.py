@@ -1,5 +1,5 @@
 # Range search on the GPU against the numpy restatement
-# tests/range_ref.py: (lims, D, I) of every row of the probed lists whose
+# oracle/range.py: (lims, D, I) of every row of the probed lists whose
 # distance passes the strict radius test, in probe-slot then arrival-id
 # order.
 #
@@ -33,15 +33,28 @@ torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
-import opq_ref  # noqa: E402
-import range_ref  # noqa: E402
-from pq4_ref import OraclePQ4  # noqa: E402
+from gpu_support import (  # noqa: E402
+    codeword_rows,
+    decode_rows,
+    engine_with,
+    ivf_spec,
+    labels,
+    queries,
+    wait_trained,
+)
 
 from distributed_faiss_amd.client import IndexClient  # noqa: E402
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
 from distributed_faiss_amd.server import IndexServer  # noqa: E402
-from oracle import make_oracle_engine  # noqa: E402
+from oracle import (  # noqa: E402
+    from_engine_artifacts,
+    range_from_scans,
+    range_search_ref,
+    ranking,
+    scan_lists,
+)
+from oracle.opq import signed_selection  # noqa: E402
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -57,25 +70,15 @@ CODEWORD_GAP = 0.05
 
 
 def _labels(rng):
-    lbl = np.repeat(np.arange(NLIST), LIST_SIZES)
-    rng.shuffle(lbl)
-    return lbl
+    return labels(rng, LIST_SIZES)
 
 
 def _queries(rng, cent, d, metric):
-    # as tests/test_gpu_dispatch_parity.py: under IP every other query is
-    # orthogonal to all centroids, so the scan's low bits reach the result
-    q = cent[rng.integers(0, NLIST, NQ)] + 0.7 * rng.standard_normal((NQ, d))
-    if metric == IP:
-        c64 = cent.astype(np.float64)
-        coef = np.linalg.lstsq(c64.T, q[::2].T, rcond=None)[0]
-        q[::2] -= (c64.T @ coef).T
-    return q.astype(np.float32)
+    return queries(rng, cent, NQ, metric)
 
 
 def _spec(typ, d, metric, **kw):
-    return dict({"type": typ, "dim": d, "metric": metric, "nlist": NLIST,
-                 "nprobe": NLIST, "seed": 1234}, **kw)
+    return ivf_spec(typ, d, metric, NLIST, **kw)
 
 
 # ---------------------------------------------------------------------------
@@ -97,32 +100,15 @@ def _pq_case(m, dsub, metric, nbits=8, f16=False, small=False):
     cb = (rng.standard_normal((m, ksub, dsub))
           * (0.1 if small else 1.0)).astype(np.float32)
     lbl = _labels(rng)
-    cw = np.empty((NROWS, m), np.int64)
-    for j in range(m):
-        c64 = cb[j].astype(np.float64)
-        gap = np.sqrt(((c64[:, None, :] - c64[None, :, :]) ** 2).sum(-1))
-        np.fill_diagonal(gap, np.inf)
-        iso = np.flatnonzero(
-            gap.min(axis=1) > CODEWORD_GAP * (0.1 if small else 1.0))
-        assert iso.size >= 8
-        cw[:, j] = rng.choice(iso, NROWS)
     # a quarter of each list repeats another row's codes: exact ties
-    for l in range(NLIST):
-        rows = np.flatnonzero(lbl == l)
-        if rows.size >= 4:
-            dup = rows[: rows.size // 4]
-            cw[dup] = cw[rng.choice(rows[rows.size // 4:], dup.size)]
-    dec = np.concatenate([cb[j][cw[:, j]] for j in range(m)], axis=1)
-    xb = (cent[lbl] + dec + (1e-4 if small else 1e-3)
+    cw = codeword_rows(rng, cb, lbl,
+                       CODEWORD_GAP * (0.1 if small else 1.0), 8)
+    xb = (cent[lbl] + decode_rows(cb, cw) + (1e-4 if small else 1e-3)
           * rng.standard_normal((NROWS, d))).astype(np.float32)
     q = _queries(rng, cent, d, metric)
     spec = _spec("ivfpq", d, metric, m=m, nbits=nbits,
                  pq_lut_f16=1 if f16 else 0)
-    if nbits == 4:
-        orc = OraclePQ4(d, NLIST, m, metric)
-    else:
-        orc = make_oracle_engine(spec)
-    orc.centroids, orc.codebooks, orc.is_trained = cent, cb, True
+    orc = from_engine_artifacts(spec, cent, cb)
     orc.add(xb)
     # CPU condition: the oracle encoded the intended codewords
     np.testing.assert_array_equal(
@@ -142,22 +128,17 @@ def _sq_case(d, metric, sq8):
         vdiff = rng.uniform(2.0, 6.0, d).astype(np.float32)
         c = rng.integers(0, 256, (NROWS, d))
         jit = rng.uniform(-0.1, 0.1, (NROWS, d))
-        resid = vmin + (c + 0.5 + jit) * (vdiff.astype(np.float64) / 255.0)
+        resid = vmin + (c + 0.5 + jit) * (vdiff.astype(np.float64) / 255)
     else:
         resid = (10.0 ** rng.uniform(-3.0, 1.0, (NROWS, d))
                  * rng.choice([-1.0, 1.0], (NROWS, d)))
     xb = (cent[lbl] + resid).astype(np.float32)
     q = _queries(rng, cent, d, metric)
     spec = _spec("ivfsq", d, metric, sq_type="8bit" if sq8 else "fp16")
-    orc = make_oracle_engine(spec)
-    orc.centroids = cent
-    if sq8:
-        orc.vmin, orc.vdiff = vmin, vdiff
-        orc.scale = (vdiff / np.float32(255.0)).astype(np.float32)
-        want = np.concatenate([c[lbl == l] for l in range(NLIST)])
-    orc.is_trained = True
+    orc = from_engine_artifacts(spec, cent, vmin=vmin, vdiff=vdiff)
     orc.add(xb)
     if sq8:  # CPU condition: the oracle's codes are the intended ones
+        want = np.concatenate([c[lbl == l] for l in range(NLIST)])
         np.testing.assert_array_equal(np.concatenate(orc.list_codes),
                                       want.astype(np.uint8))
     return {"spec": spec, "cent": cent, "cb": None, "vmin": vmin,
@@ -171,8 +152,7 @@ def _flat_case(d, metric):
     xb = (cent[lbl] + 0.5 * rng.standard_normal((NROWS, d))).astype(np.float32)
     q = _queries(rng, cent, d, L2)
     spec = _spec("ivf_flat", d, metric)
-    orc = make_oracle_engine(spec)
-    orc.centroids, orc.is_trained = cent, True
+    orc = from_engine_artifacts(spec, cent)
     orc.add(xb)
     return {"spec": spec, "cent": cent, "cb": None, "xb": xb, "q": q,
             "orc": orc, "metric": metric}
@@ -194,12 +174,8 @@ def _case(kind, *args):
 
 
 def _engine(case, **knobs):
-    eng = HipEngine(spec=dict(case["spec"], **knobs))
-    eng.set_trained(case["cent"], case["cb"], case.get("vmin"),
-                    case.get("vdiff"))
-    eng.add(case["xb"][:SPLIT])
-    eng.add(case["xb"][SPLIT:])
-    return eng
+    return engine_with(dict(case["spec"], **knobs), case["cent"], case["cb"],
+                       case.get("vmin"), case.get("vdiff"), case["xb"], SPLIT)
 
 
 def _ref(case, eng):
@@ -209,9 +185,9 @@ def _ref(case, eng):
     probes, keys = eng.coarse(case["q"], NLIST)
     assert (np.sort(probes, axis=1) == np.arange(NLIST)).all()
     if case["ref"] is None:
-        scans = range_ref.scan_lists(case["orc"], case["q"], probes, keys)
+        scans = scan_lists(case["orc"], case["q"], probes, keys)
         case["ref"] = (probes.copy(), keys.copy(), scans,
-                       range_ref.ranking(scans, case["metric"]))
+                       ranking(scans, case["metric"]))
     np.testing.assert_array_equal(case["ref"][0], probes)
     np.testing.assert_array_equal(case["ref"][1], keys)
     return case["ref"]
@@ -245,12 +221,12 @@ def _check_radii(eng, case):
         vals, ids = rank[i]
         # 1. a midpoint radius
         r = _mid_radius(vals)
-        _assert_same(run(r), range_ref.range_from_scans(scans, metric, r))
+        _assert_same(run(r), range_from_scans(scans, metric, r))
         # 2. exactly the rank-30 value: that row and its ties are dropped
         r = vals[RANK]
         lims, D, I = run(r)
         _assert_same((lims, D, I),
-                     range_ref.range_from_scans(scans, metric, r))
+                     range_from_scans(scans, metric, r))
         better = (vals < r) if metric == L2 else (vals > r)
         assert lims[i + 1] - lims[i] == better.sum() <= RANK
         assert ids[RANK] not in I[lims[i]:lims[i + 1]]
@@ -265,7 +241,7 @@ def _check_radii(eng, case):
     # 4. including radius: every row of the probed lists
     r = FLT_MAX if metric == L2 else -FLT_MAX
     lims, D, I = run(r)
-    _assert_same((lims, D, I), range_ref.range_from_scans(scans, metric, r))
+    _assert_same((lims, D, I), range_from_scans(scans, metric, r))
     assert np.array_equal(np.diff(lims), np.full(NQ, NROWS))
 
 
@@ -417,13 +393,13 @@ def test_filtered_range_bitexact(kind, metric, filt):
     allow = _allow(filt, case["orc"])
     for r in (_mid_radius(rank[0][0], 200),
               FLT_MAX if metric == L2 else -FLT_MAX):
-        want = range_ref.range_from_scans(scans, metric, r, allow[:NROWS])
+        want = range_from_scans(scans, metric, r, allow[:NROWS])
         _assert_same(eng.range_search_preassigned(
             case["q"], probes, keys, r, allow), want)
         if filt == "NONE":
             assert want[0][-1] == 0
         else:
-            assert 0 < want[0][-1] <= range_ref.range_from_scans(
+            assert 0 < want[0][-1] <= range_from_scans(
                 scans, metric, r)[0][-1]
     # under the including radius the mask alone decides: it does bite
     if filt != "NONE":
@@ -472,7 +448,7 @@ def test_duplicate_probe_list_contributes_twice(metric):
     r = FLT_MAX if metric == L2 else -FLT_MAX
     lims, D, I = eng.range_search_preassigned(case["q"], pr, ke, r)
     _assert_same((lims, D, I),
-                 range_ref.range_search_ref(case["orc"], case["q"], pr, ke, r))
+                 range_search_ref(case["orc"], case["q"], pr, ke, r))
     assert np.array_equal(np.diff(lims), np.full(NQ, 515 + 65 + 515))
     for i in range(NQ):
         seg = slice(lims[i], lims[i + 1])
@@ -491,7 +467,7 @@ def test_scan_fan_is_ignored_in_range_mode(metric):
               FLT_MAX if metric == L2 else -FLT_MAX):
         a = e1.range_search_preassigned(case["q"], probes, keys, r)
         _assert_same(e4.range_search_preassigned(case["q"], probes, keys, r), a)
-        _assert_same(a, range_ref.range_from_scans(scans, metric, r))
+        _assert_same(a, range_from_scans(scans, metric, r))
 
 
 @pytest.mark.parametrize("metric", METRICS)
@@ -500,7 +476,7 @@ def test_opq_is_the_plain_engine_behind_the_transform(metric):
     d_out = m * dsub
     case = _case("pq", m, dsub, metric, 8, False)  # data at d_out
     rng = np.random.default_rng(77)
-    A = opq_ref.signed_selection(d_in, d_out, rng)
+    A = signed_selection(d_in, d_out, rng)
     # rows whose transform is exactly the case's: x = A^T y (+ junk in the
     # dropped columns)
     junk = rng.standard_normal((NROWS + NQ, d_in)).astype(np.float32)
@@ -523,7 +499,7 @@ def test_opq_is_the_plain_engine_behind_the_transform(metric):
         want = plain.range_search_preassigned(case["q"], probes, keys, r)
         _assert_same(eng.range_search_preassigned(q, probes, keys, r), want)
         _assert_same(eng.range_search(q, r), plain.range_search(case["q"], r))
-        _assert_same(want, range_ref.range_from_scans(scans, metric, r))
+        _assert_same(want, range_from_scans(scans, metric, r))
 
 
 @pytest.mark.parametrize("metric", METRICS)
@@ -532,10 +508,8 @@ def test_deterministic_and_follows_adds(metric):
     eng = HipEngine(spec=case["spec"])
     eng.set_trained(case["cent"], None, case["vmin"], case["vdiff"])
     eng.add(case["xb"][:SPLIT])
-    orc = make_oracle_engine(case["spec"])
-    orc.centroids, orc.vmin, orc.vdiff = case["cent"], case["vmin"], case["vdiff"]
-    orc.scale = case["orc"].scale
-    orc.is_trained = True
+    orc = from_engine_artifacts(case["spec"], case["cent"],
+                                vmin=case["vmin"], vdiff=case["vdiff"])
     orc.add(case["xb"][:SPLIT])
     probes, keys = eng.coarse(case["q"], NLIST)
     r = _mid_radius(_ref(case, _engine(case))[3][0][0], 100)
@@ -543,11 +517,11 @@ def test_deterministic_and_follows_adds(metric):
     b = eng.range_search_preassigned(case["q"], probes, keys, r)
     for x, y in zip(a, b):
         assert x.tobytes() == y.tobytes()
-    _assert_same(a, range_ref.range_search_ref(orc, case["q"], probes, keys, r))
+    _assert_same(a, range_search_ref(orc, case["q"], probes, keys, r))
     eng.add(case["xb"][SPLIT:])
     orc.add(case["xb"][SPLIT:])
     c = eng.range_search_preassigned(case["q"], probes, keys, r)
-    _assert_same(c, range_ref.range_search_ref(orc, case["q"], probes, keys, r))
+    _assert_same(c, range_search_ref(orc, case["q"], probes, keys, r))
     assert c[0][-1] > a[0][-1]
     # NaN radius: empty
     lims, D, I = eng.range_search(case["q"], float("nan"))
@@ -604,7 +578,7 @@ def test_errors():
         small.range_search(q, float(FLT_MAX))
     probes, keys, scans, rank = _ref(case, small)
     r = _mid_radius(rank[0][0], 5)
-    want = range_ref.range_from_scans(scans, L2, r)
+    want = range_from_scans(scans, L2, r)
     assert 0 < want[0][-1] <= 100
     _assert_same(small.range_search(q, r), want)
 
@@ -616,19 +590,6 @@ def test_errors():
 # ---------------------------------------------------------------------------
 # Index / IndexClient over two in-process shards
 # ---------------------------------------------------------------------------
-
-
-def _wait_trained(idx):
-    import time
-
-    from distributed_faiss_amd.index_state import IndexState
-
-    t0 = time.time()
-    while time.time() - t0 < 30:
-        if idx.get_state() == IndexState.TRAINED:
-            return
-        time.sleep(0.01)
-    raise AssertionError("index did not reach TRAINED")
 
 
 @pytest.mark.parametrize("metric", ["l2", "dot"])
@@ -648,7 +609,7 @@ def test_index_and_client_two_shards(tmp_path, metric):
         meta = [("doc", s, i % 4) for i in range(n)]
         srv.add_index_data("x", xb[s * n:(s + 1) * n], meta,
                            train_async_if_triggered=False)
-        _wait_trained(srv._get_index("x"))
+        wait_trained(srv._get_index("x"))
         servers.append(srv)
     client = IndexClient(servers=servers, distributed=False)
     client.cfg = cfg

@@ -4,7 +4,7 @@
 # SAME probe lists and coarse keys the engine derives (the oracle's own IP
 # bias differs from the coarse GEMM's in the last bits; feeding it the
 # engine's keys is what keeps the base stage bitwise, as in
-# test_gpu_filtered), followed by tests/refine_ref.py over xb in the stored
+# test_gpu_filtered), followed by oracle/refine.py over xb in the stored
 # type. The base stages are bit-exact and the refine order is defined, so D
 # and I are compared BITWISE.
 #
@@ -31,10 +31,13 @@ if not torch.cuda.is_available():
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
 from oracle import make_oracle_engine  # noqa: E402
-from refine_ref import refine_ref  # noqa: E402
+from gpu_support import assert_bitwise as _bitwise  # noqa: E402
+from oracle.refine import (  # noqa: E402
+    refine_ref,
+)
 from test_gpu_filtered import (  # noqa: E402
-    _allow, _clustered, _data, _masked_ref, _oracle, _pad, _rand,
-    _wait_trained)
+    _allow, _clustered, _data, _engine as _build, _masked_ref, _oracle, _pad,
+    _rand, _wait_trained)
 
 IP, L2 = 0, 1
 NTOTAL, NLIST = 3187, 8
@@ -46,21 +49,6 @@ STORE_T = {"fp32": np.float32, "fp16": np.float16}
 # (k, k_factor, k')
 K_CASES = [(10, 1, 10), (10, 1.6, 16), (10, 1.7, 17), (10, 4, 40), (1, 1, 1),
            (40, 13, 512)]
-
-
-def _bitwise(D, I, Dr, Ir):
-    np.testing.assert_array_equal(I, Ir)
-    assert D.dtype == np.float32 and Dr.dtype == np.float32
-    np.testing.assert_array_equal(D.view(np.uint32), Dr.view(np.uint32))
-
-
-def _build(spec, art, batches):
-    eng = HipEngine(spec=spec)
-    eng.set_trained(art["cent"], art.get("codebooks"), art.get("vmin"),
-                    art.get("vdiff"))
-    for b in batches:
-        eng.add(b)
-    return eng
 
 
 class _Case:

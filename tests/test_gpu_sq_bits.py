@@ -1,6 +1,6 @@
 # 4- and 6-bit scalar quantizers (spec "sq_type": "4bit" | "6bit";
-# DESIGN.md §6h) on the GPU, against the numpy restatement
-# tests/sq_bits_ref.py. Trained artifacts are injected with set_trained and
+# DESIGN.md §6h) on the GPU, against the CPU oracle (oracle.OracleIVFSQ at
+# qtype "4bit" / "6bit"). Trained artifacts are injected with set_trained and
 # the restatement scans the lists the engine dumps (get_lists), so the
 # coarse GEMM's tolerance tier cannot move a row between lists: every
 # comparison in this file is bitwise.
@@ -22,9 +22,19 @@ if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
 from distributed_faiss_amd.hip_engine import HipEngine, HipProvider  # noqa: E402
-from range_ref import range_from_scans, ranking, scan_lists  # noqa: E402
-from refine_ref import refine_ref  # noqa: E402
-from sq_bits_ref import OracleSQBits, code_bytes, pack, stride  # noqa: E402
+from gpu_support import assert_bitwise, engine_with  # noqa: E402
+from oracle import (  # noqa: E402
+    from_engine_artifacts,
+    pack_sq,
+    range_from_scans,
+    ranking,
+    scan_lists,
+    sq_code_bytes,
+    sq_stride,
+)
+from oracle.refine import (  # noqa: E402
+    refine_ref,
+)
 
 IP, L2 = 0, 1
 METRICS = [pytest.param(IP, id="ip"), pytest.param(L2, id="l2")]
@@ -73,22 +83,14 @@ def _data(d, metric):
 
 def _engine(d, metric, bits, **kw):
     cent, xb, _q, vmin, vdiff = _data(d, metric)
-    eng = HipEngine(spec=_spec(d, metric, bits, **kw))
-    eng.set_trained(cent, None, vmin, vdiff)
-    half = xb.shape[0] // 2 + 37
-    eng.add(xb[:half])
-    eng.add(xb[half:])
-    return eng
+    return engine_with(_spec(d, metric, bits, **kw), cent, None, vmin, vdiff,
+                       xb, split=xb.shape[0] // 2 + 37)
 
 
 def _oracle(d, metric, bits, eng):
     cent, _xb, _q, vmin, vdiff = _data(d, metric)
-    orc = OracleSQBits(d, NLIST, metric, bits)
-    orc.centroids, orc.is_trained = cent, True
-    orc.set_ranges(vmin, vdiff)
-    orc.load_lists(*eng.get_lists())
-    orc.nprobe = NPROBE
-    return orc
+    return from_engine_artifacts(_spec(d, metric, bits), cent, vmin=vmin,
+                                 vdiff=vdiff, lists=eng.get_lists())
 
 
 @functools.lru_cache(maxsize=None)
@@ -122,11 +124,6 @@ def _expect_topk(case, k, allow=None):
     return D, I
 
 
-def _assert_bitwise(D, I, Do, Io):
-    np.testing.assert_array_equal(I, Io)
-    np.testing.assert_array_equal(D.view(np.uint32), Do.view(np.uint32))
-
-
 # ---------------------------------------------------------------------------
 # 1. scan
 # ---------------------------------------------------------------------------
@@ -139,7 +136,7 @@ def test_scan_bitexact(d, bits, metric):
     case = _case(d, metric, bits)
     D, I = case["eng"].search_preassigned(case["q"], case["probes"],
                                           case["keys"], K)
-    _assert_bitwise(D, I, *_expect_topk(case, K))
+    assert_bitwise(D, I, *_expect_topk(case, K))
 
 
 @pytest.mark.parametrize("metric", METRICS)
@@ -150,7 +147,7 @@ def test_selection_switch(bits, metric):
     for k in (16, 17, 1):
         D, I = case["eng"].search_preassigned(case["q"], case["probes"],
                                               case["keys"], k)
-        _assert_bitwise(D, I, *_expect_topk(case, k))
+        assert_bitwise(D, I, *_expect_topk(case, k))
 
 
 @pytest.mark.parametrize("metric", METRICS)
@@ -159,7 +156,7 @@ def test_search_equals_preassigned(bits, metric):
     case = _case(40, metric, bits)
     for k in (K, 17):
         D, I = case["eng"].search(case["q"], k)
-        _assert_bitwise(D, I, *_expect_topk(case, k))
+        assert_bitwise(D, I, *_expect_topk(case, k))
 
 
 def test_results_carry_exact_ties():
@@ -187,11 +184,11 @@ def test_stored_rows_are_the_restatements_encode(d, bits, metric):
     off, ids, codes = case["eng"].get_lists()
     n = case["n"]
     assert off[-1] == n and np.array_equal(np.sort(ids), np.arange(n))
-    assert codes.shape == (n, stride(d, bits))
+    assert codes.shape == (n, sq_stride(d, bits))
     lst = np.repeat(np.arange(NLIST), np.diff(off))
     resid = xb[ids] - cent[lst]  # fp32, the engine's own subtraction
-    want = pack(case["orc"]._encode_resid(resid), bits)
-    cb = code_bytes(d, bits)
+    want = pack_sq(case["orc"]._encode_resid(resid), bits)
+    cb = sq_code_bytes(d, bits)
     assert want.shape == (n, cb)
     np.testing.assert_array_equal(codes[:, :cb], want)
     # every bit past d * bits is zero: the tail of the last code byte and
@@ -225,7 +222,7 @@ def test_filtered_bitexact(d, bits, metric):
     for k in (K, 17):
         D, I = case["eng"].search_preassigned_filtered(
             case["q"], case["probes"], case["keys"], k, allow)
-        _assert_bitwise(D, I, *_expect_topk(case, k, allow))
+        assert_bitwise(D, I, *_expect_topk(case, k, allow))
 
 
 @pytest.mark.parametrize("metric", METRICS)
@@ -258,7 +255,7 @@ def test_range_search_bitexact(d, bits, metric):
         lims, D, I = case["eng"].range_search_preassigned(
             case["q"], case["probes"], case["keys"], radius, allow)
         np.testing.assert_array_equal(lims, lims_o)
-        _assert_bitwise(D, I, Do, Io)
+        assert_bitwise(D, I, Do, Io)
     # the distances are bitwise those `search` gives the same rows
     Ds, Is = case["eng"].search_preassigned(case["q"], case["probes"],
                                             case["keys"], 17)
@@ -286,7 +283,7 @@ def test_reconstruct_bitexact(d, bits):
     case = _case(d, L2, bits)
     D, I, R = case["eng"].search_and_reconstruct(case["q"], K)
     assert (I >= 0).all()
-    _assert_bitwise(D, I, *_expect_topk(case, K))
+    assert_bitwise(D, I, *_expect_topk(case, K))
     # centroid + (vmin + (c + 0.5) * scale), scale = vdiff / Q in fp32
     np.testing.assert_array_equal(
         R.view(np.uint32), case["orc"].decode_ids(I).view(np.uint32))
@@ -301,7 +298,7 @@ def test_refine_on_top_bitexact(bits, metric):
     D, I = eng.search(case["q"], K)
     _Do, Io = _expect_topk(case, K * kf)  # the base stage runs at k' = 40
     Dr, Ir = refine_ref(case["q"], _data(d, metric)[1], Io, K, metric)
-    _assert_bitwise(D, I, Dr, Ir)
+    assert_bitwise(D, I, Dr, Ir)
 
 
 # ---------------------------------------------------------------------------
@@ -331,7 +328,7 @@ def test_save_load_round_trip(bits, tmp_path):
     for k in (K, 17):
         D, I = eng2.search_preassigned(case["q"], case["probes"],
                                        case["keys"], k)
-        _assert_bitwise(D, I, *_expect_topk(case, k))
+        assert_bitwise(D, I, *_expect_topk(case, k))
     R2 = eng2.search_and_reconstruct(case["q"], K)[2]
     R1 = eng.search_and_reconstruct(case["q"], K)[2]
     np.testing.assert_array_equal(R2.view(np.uint32), R1.view(np.uint32))
@@ -373,17 +370,15 @@ def test_trained_ranges_equal_sq8s(bits):
     # scale = vdiff / Q in fp32: the restatement, given the engine's ranges
     # and lists, reconstructs and scans to the same bits
     eng = engs[bits]
-    orc = OracleSQBits(x.shape[1], 8, L2, bits)
-    orc.centroids, orc.is_trained = eng.get_centroids(), True
-    orc.set_ranges(vmin, vdiff)
-    orc.load_lists(*eng.get_lists())
+    orc = from_engine_artifacts(eng.spec, eng.get_centroids(), vmin=vmin,
+                                vdiff=vdiff, lists=eng.get_lists())
     q = x[:16]
     D, I, R = eng.search_and_reconstruct(q, K)
     np.testing.assert_array_equal(R.view(np.uint32),
                                   orc.decode_ids(I).view(np.uint32))
     probes, keys = eng.coarse(q, 8)
     Do, Io = orc.search_preassigned(q, probes, keys, K)
-    _assert_bitwise(D, I, Do, Io)
+    assert_bitwise(D, I, Do, Io)
 
 
 def test_reconstruction_error_orders_by_width():

@@ -1,7 +1,7 @@
 # OPQ pre-transform (spec "opq": 1), the parts that need no
 # GPU: factory strings and the knnlm builder, every refusal, the spec
 # validation in dfann_create, and the numpy restatement's own sanity
-# (tests/opq_ref.py) on the structured training recipe.
+# (oracle/opq.py) on the structured training recipe.
 import ctypes
 import functools
 import json
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from distributed_faiss_amd.engine_spec import (ENGINE_PERF_KNOBS,  # noqa: E402
                                                OPQ_KEYS, resolve_engine_spec)
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
-import opq_ref  # noqa: E402
+from oracle import opq  # noqa: E402
 
 SO = os.path.join(REPO, "distributed_faiss_amd", "libdfann.so")
 
@@ -222,38 +222,38 @@ def test_create_opq_refusals_name_the_key(lib, kw, key):
 
 @functools.lru_cache(maxsize=None)
 def _trained():
-    x = opq_ref.recipe()
-    A = opq_ref.opq_train(x, m=8, ksub=16, niter=8)
+    x = opq.recipe()
+    A = opq.opq_train(x, m=8, ksub=16, niter=8)
     return x, A
 
 
 def test_reference_rotation_is_orthonormal():
     _x, A = _trained()
     assert A.shape == (32, 32)
-    assert opq_ref.ortho_dev(A) < 1e-12
+    assert opq.ortho_dev(A) < 1e-12
     # one rounding to float32: a few ulp of 1
-    assert opq_ref.ortho_dev(A.astype(np.float32)) < 8 * 2.0 ** -23
+    assert opq.ortho_dev(A.astype(np.float32)) < 8 * 2.0 ** -23
 
 
 def test_reference_opq_beats_plain_pq():
     x, A = _trained()
-    xc = opq_ref.centred(x)
-    plain = opq_ref.pq_mse(xc, 8, 16)
-    rot = opq_ref.pq_mse(opq_ref.transform(A.astype(np.float32), xc), 8, 16)
+    xc = opq.centred(x)
+    plain = opq.pq_mse(xc, 8, 16)
+    rot = opq.pq_mse(opq.transform(A.astype(np.float32), xc), 8, 16)
     print(f"plain PQ mse {plain:.2f}, OPQ mse {rot:.2f}, ratio {rot / plain:.3f}")
     assert rot <= 0.5 * plain
 
 
 def test_reference_reduced_dim_rows_orthonormal():
-    A = opq_ref.opq_train(opq_ref.recipe(), m=8, ksub=16, d_out=16, niter=2)
+    A = opq.opq_train(opq.recipe(), m=8, ksub=16, d_out=16, niter=2)
     assert A.shape == (16, 32)
-    assert opq_ref.ortho_dev(A) < 1e-12
+    assert opq.ortho_dev(A) < 1e-12
 
 
 def test_polar_svd_is_the_nearest_orthonormal():
     rng = np.random.default_rng(3)
     M = rng.standard_normal((40, 24))
-    P = opq_ref.polar_svd(M)
+    P = opq.polar_svd(M)
     np.testing.assert_allclose(P.T @ P, np.eye(24), atol=1e-12)
     # M = P H with H symmetric positive definite
     H = P.T @ M
@@ -263,9 +263,9 @@ def test_polar_svd_is_the_nearest_orthonormal():
 
 def test_signed_selection_is_exact():
     rng = np.random.default_rng(5)
-    A = opq_ref.signed_selection(40, 24, rng)
+    A = opq.signed_selection(40, 24, rng)
     assert (np.abs(A).sum(axis=1) == 1).all() and (np.abs(A).sum(axis=0) <= 1).all()
     x = rng.standard_normal((7, 40)).astype(np.float32)
-    y = opq_ref.transform(A, x)
+    y = opq.transform(A, x)
     cols = np.abs(A).argmax(axis=1)
     np.testing.assert_array_equal(y, x[:, cols] * A[np.arange(24), cols])

@@ -1,6 +1,6 @@
 # 4-bit product quantization (spec "nbits": 4), the parts
 # that need no GPU: factory strings and the knnlm builder, the nibble
-# packing, the numpy restatement (tests/pq4_ref.py) against a float64
+# packing, the CPU oracle (oracle.OracleIVFPQ at nbits=4) against a float64
 # brute-force ADC, and the spec validation in dfann_create.
 import ctypes
 import os
@@ -15,7 +15,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from distributed_faiss_amd.engine_spec import resolve_engine_spec  # noqa: E402
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
-from pq4_ref import KSUB, OraclePQ4, pack, unpack  # noqa: E402
+from oracle import (  # noqa: E402
+    OracleIVFPQ,
+    pack_pq4 as pack,
+    unpack_pq4 as unpack,
+)
+
+KSUB = 16
 
 IP, L2 = 0, 1
 SO = os.path.join(REPO, "distributed_faiss_amd", "libdfann.so")
@@ -128,7 +134,7 @@ def test_restatement_matches_f64_adc(m, dsub, metric):
           + rng.standard_normal((n, d))).astype(np.float32)
     q = (cent[rng.integers(0, nlist, nq)]
          + rng.standard_normal((nq, d))).astype(np.float32)
-    orc = OraclePQ4(d, nlist, m, metric, seed=7)
+    orc = OracleIVFPQ(d, nlist, m, metric, 4, seed=7)
     orc.max_ppc = 32
     orc.train(xb)
     assert orc.codebooks.shape == (m, KSUB, dsub)
@@ -157,7 +163,7 @@ def test_restatement_encode_picks_the_nearest_codeword():
     m, dsub, nlist = 6, 5, 3
     d = m * dsub
     rng = np.random.default_rng(9)
-    orc = OraclePQ4(d, nlist, m, L2)
+    orc = OracleIVFPQ(d, nlist, m, L2, 4)
     orc.centroids = (rng.standard_normal((nlist, d)) * 10.0).astype(np.float32)
     orc.codebooks = rng.standard_normal((m, KSUB, dsub)).astype(np.float32)
     orc.is_trained = True

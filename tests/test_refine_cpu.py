@@ -1,5 +1,5 @@
 # Refine stage, the parts that need no GPU: factory strings and builder
-# keys, the numpy restatement of the refine kernel (tests/refine_ref.py)
+# keys, the numpy restatement of the refine kernel (oracle/refine.py)
 # against a float64 brute force and against a hand-coded scalar lane order,
 # spec validation in dfann_create, and set_k_factor through the TCP proxy.
 import ctypes
@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from distributed_faiss_amd.engine_spec import (  # noqa: E402
     ENGINE_PERF_KNOBS, REFINE_KEYS, resolve_engine_spec)
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
-from refine_ref import (  # noqa: E402
+from oracle.refine import (  # noqa: E402
     IP, L2, FLT_MAX, k_prime, refine_distances, refine_ref)
 
 SO = os.path.join(REPO, "distributed_faiss_amd", "libdfann.so")

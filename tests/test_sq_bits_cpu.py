@@ -1,6 +1,6 @@
 # 4- and 6-bit scalar quantizers (spec "sq_type": "4bit" | "6bit";
 # DESIGN.md §6h), the parts that need no GPU: the bit-stream packing with
-# hand-written known answers, the numpy restatement (tests/sq_bits_ref.py)
+# hand-written known answers, the numpy restatement (oracle.OracleIVFSQ)
 # against faiss's decode formula in float64, the factory strings, and the
 # spec handling of dfann_create.
 import ctypes
@@ -17,8 +17,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from distributed_faiss_amd.engine_spec import resolve_engine_spec  # noqa: E402
 from distributed_faiss_amd.index_cfg import IndexCfg  # noqa: E402
-from sq_bits_ref import (OracleSQBits, code_bytes, pack, stride,  # noqa: E402
-                         unpack)
+from oracle import (  # noqa: E402
+    OracleIVFSQ,
+    pack_sq as pack,
+    sq_code_bytes as code_bytes,
+    sq_stride as stride,
+    unpack_sq as unpack,
+)
 
 IP, L2 = 0, 1
 BITS = [4, 6]
@@ -87,7 +92,7 @@ def _trained(d, nlist, metric, bits, rng, n=500):
     cent = (rng.standard_normal((nlist, d)) * 3.0).astype(np.float32)
     lbl = rng.integers(0, nlist, n)
     xb = (cent[lbl] + rng.standard_normal((n, d))).astype(np.float32)
-    orc = OracleSQBits(d, nlist, metric, bits)
+    orc = OracleIVFSQ(d, nlist, metric, f"{bits}bit")
     orc.centroids = cent
     r = xb - cent[lbl]
     vmin = r.min(axis=0).astype(np.float32)
@@ -176,7 +181,7 @@ def test_restatement_search_runs_through_the_oracle_merge():
     orc.add(xb)
     off, ids, packed = orc.packed_lists()
     assert packed.shape == (500, code_bytes(d, bits)) and off[-1] == 500
-    other = OracleSQBits(d, nlist, L2, bits)
+    other = OracleIVFSQ(d, nlist, L2, f"{bits}bit")
     other.centroids, other.is_trained = orc.centroids, True
     other.set_ranges(orc.vmin, orc.vdiff)
     other.load_lists(off, ids, packed)
