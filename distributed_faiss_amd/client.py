@@ -546,6 +546,22 @@ class IndexClient:
                 self.sub_indexes[0].get_ntotal(index_id)))
         return sum(self.pool.map(lambda idx: idx.get_ntotal(index_id), self.sub_indexes))
 
+    def remove_ids(self, index_id: str, meta_ids) -> int:
+        """Remove the rows whose metadata id (the key get_ids reports) is in
+        `meta_ids` from every shard; returns the number of rows removed over
+        all shards. The rows stop being searchable at once and their ids are
+        never reused. Dist mode (one rank per shard): each rank removes from
+        its own shard and the counts are combined with all_gather_object."""
+        meta_ids = list(meta_ids)
+        if self.dist_mode:
+            from .dist import all_gather_object
+
+            return sum(all_gather_object(
+                self.sub_indexes[0].remove_by_meta_ids(index_id, meta_ids)))
+        return sum(self.pool.map(
+            lambda idx: idx.remove_by_meta_ids(index_id, meta_ids),
+            self.sub_indexes))
+
     def get_ids(self, index_id: str) -> set:
         if self.dist_mode:
             from .dist import all_gather_object

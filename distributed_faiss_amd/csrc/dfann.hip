@@ -308,7 +308,9 @@ struct dfann_index {
   float sq_q() const { return (float)((1 << sq_bits) - 1); }  // top code
   uint64_t seed = 1234;
   bool trained = false;
-  int64_t ntotal = 0;
+  int64_t ntotal = 0;    // ids ever issued (= the first id of the next add)
+  int64_t nremoved = 0;  // ids taken out again by dfann_remove_ids (§6j)
+  int64_t nlive() const { return ntotal - nremoved; }  // rows stored
   int code_bytes = 0, stride = 0;
   int ws_mb = 512;  // chunk budget for key matrices (spec "ws_mb"; tests
                     // shrink it to force the multi-chunk paths)
@@ -367,6 +369,12 @@ struct dfann_index {
   DevBuf range_D, range_I, range_ws;
   DevBuf filt_ws;    // filtered search: allow-bitmap in CSR-position space
                      // (rebuilt by k_filter_id2pos on every filtered call)
+  // removal. ivf: keep words, their popcounts and the int64
+  // prefix of one compaction. flat: the tombstones, a live bitmap over ids
+  // that exists from the first removal on (host mirror: adds extend it)
+  DevBuf rm_keep, rm_cnt, rm_prefix;
+  DevBuf flat_live;
+  std::vector<uint32_t> h_flat_live;
   // refine stage: raw rows in arrival order (row i = id i),
   // never rebuilt or moved; the base stage searches k' into rf_D / rf_I
   int refine = 0;          // spec "refine": 0 off, 1 fp32, 2 fp16
@@ -1092,8 +1100,12 @@ static dfann_index *create_from_spec(const std::string &js) {
   if (h->merge_mb < 1) h->merge_mb = 1;
   // 64 MB slabs: small enough that an empty index costs little, large
   // enough that the 1B-row table stays a few thousand L1-hot entries
-  h->csr_arena.init(h->stride, (size_t)64 << 20);
-  h->pend_arena.init(h->stride, (size_t)64 << 20);
+  // ("slab_mb" shrinks them: the window logic of rebuild_csr and of the
+  // removal compaction is only reachable in a test at a small slab size)
+  int csr_slab_mb = (int)json_int(js, "slab_mb", 64);
+  csr_slab_mb = std::min(std::max(csr_slab_mb, 1), 4096);
+  h->csr_arena.init(h->stride, (size_t)csr_slab_mb << 20);
+  h->pend_arena.init(h->stride, (size_t)csr_slab_mb << 20);
   if (h->nlist > 0) h->h_off.assign(h->nlist + 1, 0);
   // refine stage (faiss IndexRefineFlat / IndexRefine(SQfp16))
   std::string rf = json_str(js, "refine", "");
@@ -1274,11 +1286,19 @@ static void rebuild_csr(dfann_index *h, hipStream_t stream) {
     HIP_CHECK(hipMemcpyAsync(d_psrc.p, psrc.data(), (size_t)n_pend * 4,
                              hipMemcpyHostToDevice, stream));
   h->cr_ids_new.ensure((size_t)std::max<int64_t>(n_new, 1) * 8);
-  h->id2pos.ensure((size_t)std::max<int64_t>(n_new, 1) * 4);
+  // id2pos covers the id space, not the row count. A grown table starts as
+  // all sentinels: the gather rewrites every stored id, removed ids stay
+  // PAD_POS.
+  if ((size_t)h->ntotal * 4 > h->id2pos.cap) {
+    h->id2pos.ensure(std::max((size_t)h->ntotal * 4, h->id2pos.cap * 2));
+    HIP_CHECK(hipMemsetAsync(h->id2pos.p, 0xFF, h->id2pos.cap, stream));
+  }
   SlabArena next;
   next.init(h->stride, h->csr_arena.slab_bytes());
   const int64_t rps = next.rps();
-  int64_t id_base = n_old;  // pending row p arrived as id n_old + p
+  // pending row p arrived as id (ntotal - n_pend) + p: the CSR row count
+  // stops being the id base once a row was removed
+  int64_t id_base = h->ntotal - n_pend;
   size_t old_free_cursor = 0;
   const uint8_t *const *old_tab = h->csr_arena.dev_table(stream);
   const uint8_t *const *pend_tab = h->pend_arena.dev_table(stream);
@@ -1432,6 +1452,19 @@ static void refine_append(dfann_index *h, int64_t n, const float *x,
   ra.rows = row0 + n;
 }
 
+// flat tombstones: bring the live bitmap up to ntotal ids, ids from `from`
+// on live, and refresh the device copy. The host mirror is the master.
+static void flat_live_extend(dfann_index *h, int64_t from) {
+  const size_t words = (size_t)((h->ntotal + 31) / 32);
+  h->h_flat_live.resize(words, 0u);
+  for (int64_t i = from; i < h->ntotal; ++i)
+    h->h_flat_live[(size_t)(i >> 5)] |= 1u << (unsigned)(i & 31);
+  h->flat_live.grow_keep(std::max(words * 4, (size_t)16), 0);
+  if (words)
+    HIP_CHECK(hipMemcpy(h->flat_live.p, h->h_flat_live.data(), words * 4,
+                        hipMemcpyHostToDevice));
+}
+
 static void add_impl(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream) {
   if (!h->trained) throw std::runtime_error("add on untrained index");
@@ -1446,6 +1479,7 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
                              stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     h->ntotal += n;
+    if (h->nremoved) flat_live_extend(h, h->ntotal - n);
     return;
   }
   // internal chunking: bounds the residual/assign transients for huge
@@ -2132,11 +2166,12 @@ static ScanJob scan_prepare(dfann_index *h, int64_t nq, const float *q,
   a.fan = p.fan;
   if (filt) {
     // outside the scan timing events: not counted in scan_ms
-    int64_t waves = (h->ntotal + 63) / 64;
+    // (over the csr_rows positions: fewer than ntotal after a removal)
+    int64_t waves = (h->csr_rows + 63) / 64;
     h->filt_ws.ensure((size_t)waves * 8);
     hipLaunchKernelGGL(k_filter_id2pos, dim3((unsigned)((waves + 3) / 4)),
                        dim3(256), 0, stream, allow, h->cr_ids.as<int64_t>(),
-                       (long long)h->ntotal, h->filt_ws.as<unsigned>());
+                       (long long)h->csr_rows, h->filt_ws.as<unsigned>());
     a.posbits = h->filt_ws.as<unsigned>();
   }
   if (use_pre) {
@@ -2344,7 +2379,7 @@ static void range_impl(dfann_index *h, int64_t nq, const float *q_dev,
                        const int64_t **I_out, hipStream_t stream) {
   range_check(h, allow, nbits);
   *total_out = 0;
-  if (nq == 0 || h->ntotal == 0) {
+  if (nq == 0 || h->nlive() == 0) {
     HIP_CHECK(hipMemsetAsync(lims, 0, (size_t)(nq + 1) * 8, stream));
   } else {
     const float *qi = opq_queries(h, nq, q_dev, stream);
@@ -2375,7 +2410,22 @@ static void range_impl(dfann_index *h, int64_t nq, const float *q_dev,
 static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
                              float *D, int64_t *I, hipStream_t stream,
                              const uint32_t *allow = nullptr) {
-  if (h->ntotal == 0) { pad_fill(h, nq, k, D, I, stream); return; }
+  if (h->nlive() == 0) { pad_fill(h, nq, k, D, I, stream); return; }
+  // tombstones: once anything was removed every search is a
+  // filtered one, under the live bitmap or under its AND with the caller's
+  if (h->nremoved) {
+    const unsigned *live = h->flat_live.as<unsigned>();
+    if (allow) {
+      int64_t words = (h->ntotal + 31) / 32;
+      h->filt_ws.ensure((size_t)words * 4);
+      hipLaunchKernelGGL(k_bits_and, grid1d(words), dim3(256), 0, stream,
+                         allow, live, (long long)h->ntotal,
+                         h->filt_ws.as<unsigned>());
+      allow = h->filt_ws.as<unsigned>();
+    } else {
+      allow = live;
+    }
+  }
   bool ip = h->metric == M_IP;
   const int64_t CH = std::min<int64_t>(65536, std::max<int64_t>(
       4096, ((int64_t)h->ws_mb << 20) / (64 * 4)));
@@ -2455,7 +2505,7 @@ static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
     flat_search_impl(h, nq, q, k, D, I, stream, allow);
     return;
   }
-  if (h->ntotal == 0) { pad_fill(h, nq, k, D, I, stream); return; }
+  if (h->nlive() == 0) { pad_fill(h, nq, k, D, I, stream); return; }
   if (h->type == T_HNSW) { hnsw_search(h, nq, q, k, D, I, stream); return; }
   finalize_csr(h, stream);
   int nprobe = std::min(h->nprobe, h->nlist);
@@ -2519,6 +2569,127 @@ static void search_with_refine(dfann_index *h, int64_t nq, const float *q,
                      ra.rlog, ra.stride, (long long)ra.rows,
                      h->rf_I.as<int64_t>(), (long long)nq, kp, k, h->d_in, D, I);
   HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// removal
+// ---------------------------------------------------------------------------
+
+// threads per row of k_remove_compact: stride / 16 (one 16-byte unit each)
+// or 1 (a thread per row). DFANN_REMOVE_LANES=1 (A/B knob, read per call)
+// takes the thread-per-row shape; BASELINE.md "Removal" has the comparison.
+static int remove_lanes(const dfann_index *h) {
+  if (const char *e = getenv("DFANN_REMOVE_LANES"))
+    if (atoi(e) == 1) return 1;
+  return h->stride / 16;
+}
+
+// flat: tombstones. The bitmap is small (ntotal / 8 bytes) and the call
+// synchronizes anyway, so the host mirror is updated and uploaded.
+static int64_t remove_flat(dfann_index *h, const uint32_t *remove,
+                           hipStream_t stream) {
+  const size_t words = (size_t)((h->ntotal + 31) / 32);
+  std::vector<uint32_t> rm(words);
+  HIP_CHECK(hipMemcpyAsync(rm.data(), remove, words * 4, hipMemcpyDeviceToHost,
+                           stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (h->ntotal & 31) rm[words - 1] &= (1u << (unsigned)(h->ntotal & 31)) - 1u;
+  const bool have = h->nremoved > 0;
+  int64_t n = 0;
+  for (size_t w = 0; w < words; ++w) {
+    if (have) rm[w] &= h->h_flat_live[w];
+    n += __builtin_popcount(rm[w]);
+  }
+  if (n == 0) return 0;
+  if (!have) {  // first removal: everything issued so far is live
+    h->h_flat_live.assign(words, 0u);
+    flat_live_extend(h, 0);
+  }
+  for (size_t w = 0; w < words; ++w) h->h_flat_live[w] &= ~rm[w];
+  HIP_CHECK(hipMemcpy(h->flat_live.p, h->h_flat_live.data(), words * 4,
+                      hipMemcpyHostToDevice));
+  h->nremoved += n;
+  return n;
+}
+
+// ivf: physical removal. Old positions are walked in ascending windows of
+// one slab, one launch each. A kept row's new position is never past its old
+// one, so window w writes new slabs <= w only — and new slab 0 is the one
+// fresh allocation while new slab i >= 1 IS old slab i - 1, which windows
+// < w have read completely. The launches are ordered by the stream: no host
+// sync and no allocator call between windows, peak memory ~codes + one slab
+// (the bound of rebuild_csr). Old slabs past the survivors are freed at the
+// end.
+static int64_t remove_ivf(dfann_index *h, const uint32_t *remove,
+                          hipStream_t stream) {
+  finalize_csr(h, stream);  // pending rows are removable too
+  const int64_t n = h->csr_rows;
+  if (n == 0) return 0;
+  const int64_t words = (n + 63) / 64;
+  h->rm_keep.ensure((size_t)words * 8);
+  h->rm_cnt.ensure((size_t)words * 4);
+  h->rm_prefix.ensure((size_t)(words + 1) * 8);
+  auto *keepw = h->rm_keep.as<unsigned long long>();
+  auto *prefix = h->rm_prefix.as<long long>();
+  hipLaunchKernelGGL(k_remove_keep, dim3((unsigned)((words + 3) / 4)),
+                     dim3(256), 0, stream, remove, h->cr_ids.as<int64_t>(),
+                     (long long)n, keepw, h->rm_cnt.as<int>());
+  hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(256), 0, stream,
+                     h->rm_cnt.as<int>(), (long long)words, prefix);
+  HIP_CHECK(hipGetLastError());
+  int64_t kept = 0;
+  HIP_CHECK(hipMemcpyAsync(&kept, prefix + words, 8, hipMemcpyDeviceToHost,
+                           stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (kept == n) return 0;  // nothing stored was named: not a byte changes
+  h->cr_ids_new.ensure((size_t)std::max<int64_t>(kept, 1) * 8);
+  SlabArena next;
+  next.init(h->stride, h->csr_arena.slab_bytes());
+  if (next.rlog != h->csr_arena.rlog)
+    throw std::runtime_error("remove_ids: slab geometry mismatch");
+  const int64_t rps = next.rps();
+  const int lanes = remove_lanes(h);
+  SlabArena &old = h->csr_arena;
+  // kept < n, so the survivors need no more slabs than the old image has
+  const size_t n_new_slabs = (size_t)((kept + rps - 1) >> next.rlog);
+  if (n_new_slabs > old.slabs.size())
+    throw std::runtime_error("remove_ids: slab count mismatch");
+  if (n_new_slabs) next.ensure_rows(1);  // the fresh slab
+  for (size_t i = 1; i < n_new_slabs; ++i) next.slabs.push_back(old.slabs[i - 1]);
+  next.table_dirty = true;
+  const uint8_t *const *old_tab = old.dev_table(stream);
+  uint8_t *const *new_tab = next.dev_table_mut(stream);
+  for (int64_t p0 = 0; p0 < n; p0 += rps) {
+    const int64_t p1 = std::min(n, p0 + rps);
+    hipLaunchKernelGGL(k_remove_compact, grid1d((p1 - p0) * lanes, 256, 1LL << 30),
+                       dim3(256), 0, stream, (long long)p0, (long long)p1,
+                       lanes, keepw, prefix, (long long)words, old_tab, new_tab,
+                       h->cr_ids.as<int64_t>(), h->cr_ids_new.as<int64_t>(),
+                       h->id2pos.as<unsigned>(), next.rlog, h->stride);
+    HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_remove_off, grid1d(h->nlist + 1), dim3(256), 0, stream,
+                     keepw, prefix, (long long)words, h->cr_off.as<int64_t>(),
+                     h->nlist);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(h->h_off.data(), h->cr_off.p,
+                           (size_t)(h->nlist + 1) * 8, hipMemcpyDeviceToHost,
+                           stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  // old slabs [0, n_new_slabs - 1) live on in `next`; reset frees the rest
+  for (size_t i = 1; i < n_new_slabs; ++i) old.slabs[i - 1] = nullptr;
+  old.reset();
+  std::swap(old.stride, next.stride);
+  std::swap(old.rlog, next.rlog);
+  std::swap(old.slabs, next.slabs);
+  old.rows = kept;
+  old.table_dirty = true;
+  next.rows = 0;
+  h->csr_rows = kept;
+  std::swap(h->cr_ids.p, h->cr_ids_new.p);
+  std::swap(h->cr_ids.cap, h->cr_ids_new.cap);
+  h->nremoved += n - kept;
+  return n - kept;
 }
 
 // ---------------------------------------------------------------------------
@@ -2621,7 +2792,7 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
-                       if (h->ntotal == 0) {
+                       if (h->nlive() == 0) {
                          pad_fill(h, nq, kb, Db, Ib, s);
                          return;
                        }
@@ -2667,7 +2838,7 @@ extern "C" int dfann_search_preassigned_filtered(
   const float *qi = opq_queries(h, nq, q_dev, s);
   search_with_refine(h, nq, q_dev, k, D_dev, I_dev, s,
                      [&](int kb, float *Db, int64_t *Ib) {
-                       if (h->ntotal == 0) {
+                       if (h->nlive() == 0) {
                          pad_fill(h, nq, kb, Db, Ib, s);
                          return;
                        }
@@ -2675,6 +2846,27 @@ extern "C" int dfann_search_preassigned_filtered(
                        scan_and_merge(h, nq, qi, nprobe, probes_dev,
                                       keys_dev, kb, Db, Ib, s, allow_bits_dev);
                      });
+  API_END
+}
+
+extern "C" int dfann_remove_ids(dfann_index *h, const uint32_t *remove_bits_dev,
+                                int64_t nbits, int64_t *nremoved_out,
+                                dfann_stream stream) {
+  API_BEGIN
+  if (nremoved_out) *nremoved_out = 0;
+  if (h->type == T_HNSW)
+    throw std::runtime_error("remove_ids unsupported for hnswsq");
+  if (!remove_bits_dev) throw std::runtime_error("remove_ids: null bitmap");
+  if (nbits < h->ntotal)
+    throw std::runtime_error(
+        "remove_ids: bitmap covers " + std::to_string(nbits) +
+        " ids but the index holds " + std::to_string(h->ntotal));
+  // an untrained ivf index and an index without rows have nothing to remove
+  if (!h->trained || h->nlive() == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  int64_t n = h->type == T_FLAT ? remove_flat(h, remove_bits_dev, s)
+                                : remove_ivf(h, remove_bits_dev, s);
+  if (nremoved_out) *nremoved_out = n;
   API_END
 }
 
@@ -2797,6 +2989,7 @@ extern "C" int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
 }
 
 extern "C" int64_t dfann_ntotal(dfann_index *h) { return h->ntotal; }
+extern "C" int64_t dfann_nlive(dfann_index *h) { return h->nlive(); }
 extern "C" int dfann_nlist(dfann_index *h) { return h->nlist; }
 extern "C" int dfann_is_trained(dfann_index *h) { return h->trained ? 1 : 0; }
 extern "C" int dfann_dim(dfann_index *h) { return h->d_in; }
@@ -2834,10 +3027,10 @@ extern "C" int dfann_get_lists(dfann_index *h, int64_t *off_host,
     throw std::runtime_error("hnswsq index has no inverted lists");
   finalize_csr(h, 0);
   memcpy(off_host, h->h_off.data(), (size_t)(h->nlist + 1) * 8);
-  if (h->ntotal) {
-    HIP_CHECK(hipMemcpy(ids_host, h->cr_ids.p, (size_t)h->ntotal * 8,
+  if (h->csr_rows) {  // == nlive once finalized
+    HIP_CHECK(hipMemcpy(ids_host, h->cr_ids.p, (size_t)h->csr_rows * 8,
                         hipMemcpyDeviceToHost));
-    h->csr_arena.copy_rows_to_host(codes_host, 0, h->ntotal);
+    h->csr_arena.copy_rows_to_host(codes_host, 0, h->csr_rows);
   }
   API_END
 }
@@ -3005,7 +3198,11 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
   FILE *f = fopen(path, "wb");
   if (!f) throw std::runtime_error(std::string("cannot open ") + path);
   try {
-    const uint64_t magic = 0x31304E4E414644ULL;  // "DFANN01"
+    // "DFANN01" as ever until something was removed; "DFANN02" after
+    // (DESIGN.md §6j): nlive follows ntotal, the CSR sections hold nlive
+    // rows, flat appends its live bitmap, the refine store keeps ntotal rows
+    const bool v2 = h->nremoved > 0;
+    const uint64_t magic = v2 ? 0x32304E4E414644ULL : 0x31304E4E414644ULL;
     fwrite_chk(&magic, 8, f);
     uint64_t jlen = h->spec_json.size();
     fwrite_chk(&jlen, 8, f);
@@ -3020,6 +3217,10 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
     uint8_t tr = h->trained ? 1 : 0;
     fwrite_chk(&tr, 1, f);
     fwrite_chk(&h->ntotal, 8, f);
+    if (v2) {
+      const int64_t nlive = h->nlive();
+      fwrite_chk(&nlive, 8, f);
+    }
     if (h->trained && h->type != T_FLAT) {
       if (h->type != T_HNSW)
         dump_dev(f, h->centroids, (size_t)h->nlist * h->d * 4);
@@ -3053,15 +3254,18 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
       dump_dev(f, h->hn_nbrU, (size_t)h->hnsw_nslots * HNSW_MAXL * h->m * 4);
     } else if (h->type == T_FLAT) {
       dump_dev(f, h->flat, (size_t)h->ntotal * h->d * 4);
+      if (v2)
+        fwrite_chk(h->h_flat_live.data(), (size_t)((h->ntotal + 31) / 32) * 4,
+                   f);
     } else if (h->ntotal) {
       fwrite_chk(h->h_off.data(), (size_t)(h->nlist + 1) * 8, f);
-      dump_dev(f, h->cr_ids, (size_t)h->ntotal * 8);
+      dump_dev(f, h->cr_ids, (size_t)h->csr_rows * 8);
       // codes: slab arena -> file in CSR row order (same byte layout as
       // the round-1 contiguous image)
       const int64_t CHROWS = std::max<int64_t>(1, ((int64_t)64 << 20) / h->stride);
       std::vector<char> tmp((size_t)CHROWS * h->stride);
-      for (int64_t r = 0; r < h->ntotal; r += CHROWS) {
-        int64_t c = std::min(CHROWS, h->ntotal - r);
+      for (int64_t r = 0; r < h->csr_rows; r += CHROWS) {
+        int64_t c = std::min(CHROWS, h->csr_rows - r);
         h->csr_arena.copy_rows_to_host(tmp.data(), r, c);
         fwrite_chk(tmp.data(), (size_t)c * h->stride, f);
       }
@@ -3095,7 +3299,8 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
   try {
     uint64_t magic;
     fread_chk(&magic, 8, f);
-    if (magic != 0x31304E4E414644ULL)
+    const bool v2 = magic == 0x32304E4E414644ULL;  // "DFANN02": see dfann_save
+    if (magic != 0x31304E4E414644ULL && !v2)
       throw std::runtime_error("bad dfann file magic");
     uint64_t jlen;
     fread_chk(&jlen, 8, f);
@@ -3108,6 +3313,11 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
     uint8_t tr;
     fread_chk(&tr, 1, f);
     fread_chk(&h->ntotal, 8, f);
+    int64_t nlive = h->ntotal;
+    if (v2) fread_chk(&nlive, 8, f);
+    if (nlive < 0 || nlive > h->ntotal)
+      throw std::runtime_error("dfann file: nlive outside 0..ntotal");
+    h->nremoved = h->ntotal - nlive;
     h->trained = tr != 0;
     if (h->trained && h->type == T_HNSW) {
       load_dev(f, h->sq_vmin, (size_t)h->d * 4);
@@ -3178,34 +3388,45 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
       }
     } else if (h->type == T_FLAT) {
       load_dev(f, h->flat, (size_t)h->ntotal * h->d * 4);
+      if (v2) {
+        h->h_flat_live.resize((size_t)((h->ntotal + 31) / 32));
+        fread_chk(h->h_flat_live.data(), h->h_flat_live.size() * 4, f);
+        flat_live_extend(h, h->ntotal);  // uploads; sets nothing
+      }
     } else if (h->ntotal) {
       h->h_off.resize(h->nlist + 1);
       fread_chk(h->h_off.data(), (size_t)(h->nlist + 1) * 8, f);
-      load_dev(f, h->cr_ids, (size_t)h->ntotal * 8);
+      if (h->h_off[0] != 0 || h->h_off[h->nlist] != nlive)
+        throw std::runtime_error("dfann file: list offsets do not end at nlive");
+      load_dev(f, h->cr_ids, (size_t)nlive * 8);
       {
         // codes: file (CSR row order) -> slab arena
         const int64_t CHROWS =
             std::max<int64_t>(1, ((int64_t)64 << 20) / h->stride);
         std::vector<char> tmp((size_t)CHROWS * h->stride);
-        for (int64_t r = 0; r < h->ntotal; r += CHROWS) {
-          int64_t c = std::min(CHROWS, h->ntotal - r);
+        for (int64_t r = 0; r < nlive; r += CHROWS) {
+          int64_t c = std::min(CHROWS, nlive - r);
           fread_chk(tmp.data(), (size_t)c * h->stride, f);
           h->csr_arena.copy_rows_from_host(tmp.data(), r, c);
         }
-        h->csr_arena.rows = h->ntotal;
-        h->csr_rows = h->ntotal;
+        h->csr_arena.rows = nlive;
+        h->csr_rows = nlive;
       }
       h->cr_off.ensure((size_t)(h->nlist + 1) * 8);
       HIP_CHECK(hipMemcpy(h->cr_off.p, h->h_off.data(),
                           (size_t)(h->nlist + 1) * 8, hipMemcpyHostToDevice));
       h->id2pos.ensure((size_t)h->ntotal * 4);
-      std::vector<int64_t> ids(h->ntotal);
-      HIP_CHECK(hipMemcpy(ids.data(), h->cr_ids.p, (size_t)h->ntotal * 8,
-                          hipMemcpyDeviceToHost));
-      std::vector<unsigned> i2p(h->ntotal);
-      for (int l = 0; l < h->nlist; ++l)
-        for (int64_t j = h->h_off[l]; j < h->h_off[l + 1]; ++j)
-          i2p[ids[j]] = (unsigned)j;
+      std::vector<int64_t> ids(nlive);
+      if (nlive)
+        HIP_CHECK(hipMemcpy(ids.data(), h->cr_ids.p, (size_t)nlive * 8,
+                            hipMemcpyDeviceToHost));
+      // removed ids keep the sentinel
+      std::vector<unsigned> i2p(h->ntotal, 0xFFFFFFFFu);
+      for (int64_t j = 0; j < nlive; ++j) {
+        if ((uint64_t)ids[j] >= (uint64_t)h->ntotal)
+          throw std::runtime_error("dfann file: stored id outside 0..ntotal");
+        i2p[ids[j]] = (unsigned)j;
+      }
       HIP_CHECK(hipMemcpy(h->id2pos.p, i2p.data(), (size_t)h->ntotal * 4,
                           hipMemcpyHostToDevice));
       HIP_CHECK(hipDeviceSynchronize());

@@ -2870,6 +2870,107 @@ extern "C" __global__ void k_rebuild_gather(
   id2pos[id] = (unsigned)j;
 }
 
+// ---------------------------------------------------------------------------
+// removal: one global stable stream compaction over CSR
+// positions. keep bits -> int64 prefix over the 64-position words -> every
+// kept row moves to newpos(p) = prefix[p >> 6] + popc(word & lanes below).
+// No per-list work, no atomics: the same input gives the same bytes.
+// ---------------------------------------------------------------------------
+
+// k_filter_id2pos with the sense inverted: keep[p] = !remove[cr_ids[p]],
+// one 64-bit ballot word per wave plus its popcount (the scan's input). The
+// tail wave masks p >= rows to 0; keepw and cnt hold ceil(rows / 64) entries.
+extern "C" __global__ __launch_bounds__(256) void k_remove_keep(
+    const unsigned *__restrict__ remove, const int64_t *__restrict__ cr_ids,
+    long long rows, unsigned long long *__restrict__ keepw,
+    int *__restrict__ cnt) {
+  long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bit = false;
+  if (p < rows) bit = !pos_allowed(remove, cr_ids[p]);
+  unsigned long long b = __ballot(bit);
+  if ((threadIdx.x & 63) == 0 && p < rows) {
+    keepw[p >> 6] = b;
+    cnt[p >> 6] = __popcll(b);
+  }
+}
+
+// single block: word popcounts -> exclusive int64 prefix, prefix[words] =
+// rows kept (fixed order, the range path's scan)
+__global__ __launch_bounds__(256) void k_remove_scan(
+    const int *__restrict__ cnt, long long words,
+    long long *__restrict__ prefix) {
+  long long t = block_excl_scan<int>(cnt, words, prefix);
+  if (threadIdx.x == 0) prefix[words] = t;
+}
+
+// kept rows in front of position p (p == rows included: the total)
+__device__ __forceinline__ long long remove_newpos(
+    const unsigned long long *__restrict__ keepw,
+    const long long *__restrict__ prefix, long long words, long long p) {
+  long long w = p >> 6;
+  if (w >= words) return prefix[words];
+  unsigned long long below = keepw[w] & ((1ULL << (p & 63)) - 1ULL);
+  return prefix[w] + __popcll(below);
+}
+
+// list offsets after a global stable compaction: off[l] = newpos(off[l]),
+// empty lists and l == nlist included (in place, one thread per entry)
+extern "C" __global__ void k_remove_off(
+    const unsigned long long *__restrict__ keepw,
+    const long long *__restrict__ prefix, long long words,
+    int64_t *__restrict__ off, int nlist) {
+  int l = blockIdx.x * blockDim.x + threadIdx.x;
+  if (l > nlist) return;
+  off[l] = remove_newpos(keepw, prefix, words, off[l]);
+}
+
+// Old positions [p0, p1) -> the new arena. `lanes` threads share a row, each
+// copying every lanes-th 16-byte unit of its stride (lanes = stride / 16: one
+// unit per thread, loads and stores of neighbouring lanes adjacent; lanes =
+// 1: one thread per row as in k_rebuild_gather). The row's first thread also
+// writes new_ids[newpos] and id2pos[id] (PAD_POS for a removed row).
+extern "C" __global__ __launch_bounds__(256) void k_remove_compact(
+    long long p0, long long p1, int lanes,
+    const unsigned long long *__restrict__ keepw,
+    const long long *__restrict__ prefix, long long words,
+    const uint8_t *const *__restrict__ old_slabs,
+    uint8_t *const *__restrict__ new_slabs,
+    const int64_t *__restrict__ old_ids, int64_t *__restrict__ new_ids,
+    unsigned *__restrict__ id2pos, int rlog, int stride) {
+  unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned r = t / (unsigned)lanes;
+  int c0 = (int)(t - r * (unsigned)lanes);
+  long long p = p0 + (long long)r;
+  if (p >= p1) return;
+  bool keep = (keepw[p >> 6] >> (unsigned)(p & 63)) & 1ULL;
+  long long np = keep ? remove_newpos(keepw, prefix, words, p) : -1;
+  if (c0 == 0) {
+    long long id = old_ids[p];
+    id2pos[id] = keep ? (unsigned)np : PAD_POS;
+    if (keep) new_ids[np] = id;
+  }
+  if (!keep) return;
+  const uint4 *sp =
+      reinterpret_cast<const uint4 *>(slab_row(old_slabs, rlog, p, stride));
+  uint4 *dp = reinterpret_cast<uint4 *>(slab_row_mut(new_slabs, rlog, np, stride));
+  for (int c = c0; c < stride / 16; c += lanes) dp[c] = sp[c];
+}
+
+// out = a & b over nbits bits (flat filtered search under tombstones: the
+// caller's allow bitmap AND the live bitmap). One thread per 32-bit word; the
+// bits of the last word at and past nbits come out 0.
+extern "C" __global__ void k_bits_and(const unsigned *__restrict__ a,
+                                      const unsigned *__restrict__ b,
+                                      long long nbits,
+                                      unsigned *__restrict__ out) {
+  long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long words = (nbits + 31) >> 5;
+  if (w >= words) return;
+  unsigned v = a[w] & b[w];
+  if (w == words - 1 && (nbits & 31)) v &= (1u << (unsigned)(nbits & 31)) - 1u;
+  out[w] = v;
+}
+
 // gather rows by index (f32): out[i] = in[idx[i]]
 extern "C" __global__ void k_gather_rows(const float *__restrict__ in,
                                          const int64_t *__restrict__ idx,

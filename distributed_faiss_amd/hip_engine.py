@@ -95,6 +95,10 @@ def load_lib():
                                           c.c_void_p]
     lib.dfann_ntotal.argtypes = [c.c_void_p]
     lib.dfann_ntotal.restype = c.c_int64
+    lib.dfann_nlive.argtypes = [c.c_void_p]
+    lib.dfann_nlive.restype = c.c_int64
+    lib.dfann_remove_ids.argtypes = [c.c_void_p, c.c_void_p, c.c_int64,
+                                     P(c.c_int64), c.c_void_p]
     lib.dfann_nlist.argtypes = [c.c_void_p]
     lib.dfann_is_trained.argtypes = [c.c_void_p]
     lib.dfann_dim.argtypes = [c.c_void_p]
@@ -197,6 +201,12 @@ class HipEngine:
     @property
     def ntotal(self):
         return int(self.lib.dfann_ntotal(self.h))
+
+    @property
+    def nlive(self):
+        """Rows stored: ntotal (the ids ever issued) minus the rows
+        remove_ids took out."""
+        return int(self.lib.dfann_nlive(self.h))
 
     @property
     def nlist(self):
@@ -377,6 +387,47 @@ class HipEngine:
             self._stream(torch)))
         return D.cpu().numpy(), I.cpu().numpy()
 
+    # -- removal -------------------------------------------
+
+    def remove_ids(self, ids_or_mask):
+        """faiss Index.remove_ids: take rows out by arrival id. Accepts an
+        integer array of ids (ids outside 0..ntotal-1 are an error), a bool
+        mask over ids (any length; entries past ntotal are ignored), or a
+        PackedFilter whose set bits name the rows to remove (nbits >=
+        ntotal). Returns the number of rows this call removed; ids are
+        never renumbered or reused."""
+        if isinstance(ids_or_mask, PackedFilter):
+            f = ids_or_mask
+        else:
+            a = np.asarray(ids_or_mask)
+            n = self.ntotal
+            mask = np.zeros(n, dtype=bool)
+            if a.dtype == bool:
+                a = a.reshape(-1)[:n]
+                mask[:a.shape[0]] = a
+            elif a.size:
+                if not np.issubdtype(a.dtype, np.integer):
+                    raise TypeError("remove_ids: ids must be integers or a "
+                                    "bool mask")
+                a = a.reshape(-1).astype(np.int64)
+                if a.min() < 0 or a.max() >= n:
+                    raise ValueError(
+                        f"remove_ids: id outside 0..{n - 1} (ntotal = {n})")
+                mask[a] = True
+            f = self.pack_filter(mask)
+        return self.remove_ids_dev(f.bits, f.nbits)
+
+    def remove_ids_dev(self, bits_t, nbits):
+        """Device-resident removal: bits_t is an int32 cuda tensor holding
+        the bitmap words of the ids to remove, nbits the number of ids it
+        covers. The call synchronizes the stream."""
+        torch = _torch()
+        n = ctypes.c_int64(0)
+        _check(self.lib, self.lib.dfann_remove_ids(
+            self.h, ctypes.c_void_p(bits_t.data_ptr()), int(nbits),
+            ctypes.byref(n), self._stream(torch)))
+        return int(n.value)
+
     # -- range search (DESIGN.md §6g) --------------------------------------
 
     def range_search(self, q, radius, allow=None):
@@ -473,7 +524,7 @@ class HipEngine:
         self.lib.dfann_get_lists.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 3
         self.lib.dfann_code_stride.argtypes = [ctypes.c_void_p]
         stride = int(self.lib.dfann_code_stride(self.h))
-        n = self.ntotal
+        n = self.nlive  # == ntotal until a row is removed
         off = np.empty(self.nlist + 1, dtype=np.int64)
         ids = np.empty(max(n, 1), dtype=np.int64)
         codes = np.empty((max(n, 1), stride), dtype=np.uint8)

@@ -75,7 +75,9 @@ class Index:
         self._filter_lock = threading.Lock()
 
         self.index_save_time = time.time()
-        self.index_saved_size = 0
+        # (ntotal, nlive) of the engine at the last save: a removal changes
+        # the second and leaves the first
+        self.index_saved_size = (0, 0)
 
         if cfg.save_interval_sec > 0:
             self._run_save_watcher()
@@ -128,7 +130,8 @@ class Index:
         index_total = 0
         with self.index_lock:
             if self.engine is not None:
-                index_total = self.engine.ntotal
+                # live rows: ntotal until something is removed
+                index_total = self._engine_counts()[1]
         return buf_total, index_total
 
     def train(self) -> None:
@@ -292,6 +295,56 @@ class Index:
         with self.buffer_lock:
             meta = [self.id_to_metadata[i] for i in indexes]
         return lims, scores, indexes, meta
+
+    # -- removal -----------------------------------------------------------
+
+    def remove_ids(self, ids) -> int:
+        """faiss Index.remove_ids over shard-local arrival ids (the ids
+        search_full returns). The rows leave the engine and their metadata
+        entries become None, so get_ids, metadata_for and the filter
+        predicate stop seeing them; ids are never reused. Returns the number
+        of rows removed by this call."""
+        ids = np.unique(np.asarray(ids, dtype=np.int64).reshape(-1))
+        with self.buffer_lock, self.index_lock:
+            engine = self._removable_engine()
+            return self._remove_locked(engine, ids)
+
+    def remove_by_meta_ids(self, meta_ids) -> int:
+        """Remove the rows whose metadata id — meta[cfg.custom_meta_id_idx],
+        the key get_ids reports — is in `meta_ids`. Rows still waiting in
+        the add buffer are not in the engine yet and are left alone."""
+        wanted = set(meta_ids)
+        id_idx = self.cfg.custom_meta_id_idx
+        with self.buffer_lock, self.index_lock:
+            engine = self._removable_engine()
+            ids = np.fromiter(
+                (i for i, m in enumerate(self.id_to_metadata[:engine.ntotal])
+                 if m and m[id_idx] in wanted), dtype=np.int64)
+            return self._remove_locked(engine, ids)
+
+    def _removable_engine(self):
+        # caller holds index_lock
+        if self.state != IndexState.TRAINED:
+            raise RuntimeError(f"Server index is not trained. state: {self.state}")
+        if not hasattr(self.engine, "remove_ids"):
+            raise NotImplementedError(
+                f"engine {type(self.engine).__name__} has no remove_ids: "
+                "removal needs the HIP engine")
+        return self.engine
+
+    def _remove_locked(self, engine, ids) -> int:
+        # caller holds buffer_lock and index_lock
+        if ids.size == 0:
+            return 0
+        removed = int(engine.remove_ids(ids))
+        for i in ids:
+            self.id_to_metadata[i] = None
+        return removed
+
+    def _engine_counts(self) -> Tuple[int, int]:
+        # (ntotal, nlive); an engine without removal stores all it issued
+        ntotal = self.engine.ntotal
+        return ntotal, getattr(self.engine, "nlive", ntotal)
 
     @staticmethod
     def _filter_allows(m, filter_pos, filter_value) -> bool:
@@ -484,7 +537,7 @@ class Index:
                 return False
 
         with self.buffer_lock, self.index_lock:
-            if self.engine.ntotal == self.index_saved_size:
+            if self._engine_counts() == self.index_saved_size:
                 return False
             index_storage_dir = self.cfg.index_storage_dir
             index_file, meta_file, buffer_file, cfg_file = get_index_files(index_storage_dir)
@@ -496,7 +549,7 @@ class Index:
                 pickle.dump(self.embeddings_buffer, f)
             with open(cfg_file, mode="w") as f:
                 f.write(self.cfg.to_json_string() + "\n")
-            self.index_saved_size = self.engine.ntotal
+            self.index_saved_size = self._engine_counts()
             self.index_save_time = time.time()
             return True
 

@@ -176,6 +176,15 @@ class IndexServer:
         return index.range_search(query_batch, radius, filter_pos,
                                   filter_value)
 
+    def remove_ids(self, index_id: str, ids) -> int:
+        """Remove rows by shard-local arrival id (Index.remove_ids)."""
+        return self._get_index(index_id).remove_ids(ids)
+
+    def remove_by_meta_ids(self, index_id: str, meta_ids) -> int:
+        """Remove the rows whose metadata id is in `meta_ids`
+        (Index.remove_by_meta_ids); returns this shard's count."""
+        return self._get_index(index_id).remove_by_meta_ids(meta_ids)
+
     def search_ids_dev(self, index_id: str, qt, top_k: int):
         """Device-resident (D, I) search — the distributed client's timed
         serving step (no metadata epilogue, results stay in HBM)."""
@@ -213,6 +222,11 @@ class IndexServer:
                 return 0
             index = self.indexes[index_id]
         return index.get_idx_data_num()[1]
+
+    def get_nlive(self, index_id: str) -> int:
+        """Rows stored in this shard's engine (what get_ntotal reports:
+        removed rows do not count)."""
+        return self.get_ntotal(index_id)
 
     def get_aggregated_ntotal(self, index_id: str) -> int:
         with self.indexes_lock:

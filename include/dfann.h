@@ -113,6 +113,9 @@ typedef void *dfann_stream;             /* hipStream_t */
  * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int,
  * "nbits": 4|8, "sq_type": "fp16"|"8bit"|"6bit"|"4bit", "nprobe": int,
  * "seed": int}.
+ * "slab_mb" (ivf types; default 64, clamped to 1..4096): size of the slabs
+ * the inverted-list codes and the pending appends live in; the list merge
+ * and dfann_remove_ids work through them one slab at a time.
  * "ivfpq" codes: "nbits" (default 8) bits per sub-quantizer, 1 << nbits
  * codewords each; any other value is an error. At 8 a row is m bytes; at
  * 4 it is (m + 1) / 2 bytes, byte b = code[2b] |
@@ -229,6 +232,38 @@ int dfann_search_preassigned_filtered(dfann_index *h, int64_t nq,
         const float *keys_dev, int k, const uint32_t *allow_bits_dev,
         int64_t nbits, float *D_dev, int64_t *I_dev, dfann_stream stream);
 
+/* Mirrors faiss Index::remove_ids(IDSelectorBitmap). Removes every stored row
+ * whose arrival id is set in remove_bits_dev (dfann_search_filtered's bitmap
+ * convention; nbits >= ntotal else an error; bits at or past ntotal and bits
+ * of ids already removed are ignored). *nremoved_out = rows removed by THIS
+ * call. Synchronizes the stream; not graph-capturable. Deviation: faiss
+ * IndexFlat renumbers the survivors and faiss IVF re-issues ids after a
+ * removal; here an id is never renumbered and never issued twice.
+ * After the call no entry point returns a removed id (search, preassigned,
+ * filtered, range, reconstruct, refine, dfann_get_lists); dfann_ntotal is
+ * unchanged and the next add issues ids from it upward; dfann_nlive drops by
+ * *nremoved_out. A call that removes nothing (no bit set, ids already
+ * removed, an index without rows, an untrained ivf index) returns 0 and
+ * leaves the index bitwise as it was.
+ * ivf_flat / ivfpq / ivfsq: rows are removed PHYSICALLY. Rows
+ * still pending from an add are merged first; then the inverted lists are
+ * compacted (one fresh slab, then the old slabs reused behind the read
+ * window), stably — inside a list the survivors keep
+ * ascending arrival id — so the offsets, ids and code bytes are the
+ * pre-removal dump with the removed rows deleted, and every later search
+ * reads fewer bytes. Peak memory: the codes plus one slab ("slab_mb").
+ * Refine store: indexed by arrival id, it never moves; removed rows stay as
+ * unreferenced holes, their memory is not reclaimed, and dfann_refine_info
+ * still reports ntotal rows.
+ * flat: ids are positions in the raw arena, so removal leaves tombstones: a
+ * device live-bitmap over ids, allocated by the first removal, under which
+ * every later search runs the filtered top-k kernels (dfann_search_filtered
+ * ANDs it with the caller's bitmap). Arena memory is not reclaimed.
+ * Errors: hnswsq ("remove_ids unsupported for hnswsq": unlinking a graph
+ * node is a different algorithm), nbits < ntotal, a NULL bitmap. */
+int dfann_remove_ids(dfann_index *h, const uint32_t *remove_bits_dev,
+                     int64_t nbits, int64_t *nremoved_out, dfann_stream stream);
+
 /* Range search. Mirrors faiss Index::range_search over an
  * IVF index: every row of the min(nprobe, nlist, 512) probed lists whose
  * distance passes the STRICT radius test — L2: dist < radius (squared L2,
@@ -286,7 +321,11 @@ int dfann_refine_info(dfann_index *h, int64_t out[3]);
  * (pad bytes are zero). Test plumbing. */
 int dfann_get_refine_rows(dfann_index *h, int64_t row0, int64_t n,
                           void *out_host);
-int64_t dfann_ntotal(dfann_index *h);             /* faiss .ntotal */
+/* ids ever issued = the first id of the next add (faiss .ntotal until a row
+ * is removed; removal never lowers it) */
+int64_t dfann_ntotal(dfann_index *h);
+/* rows stored: ntotal minus the rows dfann_remove_ids took out */
+int64_t dfann_nlive(dfann_index *h);
 int dfann_nlist(dfann_index *h);                  /* faiss .nlist */
 int dfann_is_trained(dfann_index *h);
 int dfann_dim(dfann_index *h); /* the caller-facing dim (d_in under opq) */
@@ -300,7 +339,11 @@ const char *dfann_spec_json(dfann_index *h);
 int dfann_get_centroids(dfann_index *h, float *out_host);
 
 /* --- persistence (replaces faiss read_index/write_index at ref
- *     index.py:297,460; our own file format) --- */
+ *     index.py:297,460; our own file format).
+ *     An index nothing was ever removed from writes magic "DFANN01", byte
+ *     for byte as before; after a removal the magic is "DFANN02": nlive
+ *     follows ntotal, the list sections hold nlive rows, flat appends its
+ *     live bitmap, the refine store keeps ntotal rows. Both load. --------- */
 int dfann_save(dfann_index *h, const char *path);
 int dfann_load(const char *path, dfann_index **out);
 
@@ -330,7 +373,8 @@ int dfann_transform_info(dfann_index *h, int64_t out[3]);
  * (m,16,dsub) at nbits=4 — for dfann_set_trained and dfann_get_codebooks */
 int dfann_get_codebooks(dfann_index *h, float *out_host);
 /* Dump the finalized inverted lists to host: off (nlist+1 i64), ids
- * (ntotal i64, arrival ids in CSR order), codes (ntotal * stride u8).
+ * (nlive i64, arrival ids in CSR order), codes (nlive * stride u8) —
+ * nlive = dfann_nlive, which equals ntotal until a row is removed.
  * stride = code_bytes rounded up to 16 (ivfpq nbits=4 and ivfsq "6bit" /
  * "4bit": packed rows, see dfann_create). Used by the CPU-baseline leg of
  * bench.py to scan the SAME index content the GPU holds. */
