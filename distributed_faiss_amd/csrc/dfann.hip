@@ -437,6 +437,25 @@ static bool merge_wave_ok(int k, int64_t C) {
   return use_regsel(k) && C <= 256;
 }
 
+// The three selection paths of the merges (k_merge_cand* / k_merge_shards*)
+// and their launch shape, all at 256 threads: wave-per-query (4 queries a
+// block, no LDS), register path, LDS selection. `first` is the fastest
+// path the caller admits; the slower ones follow in this order.
+enum MergePath { MERGE_WAVE, MERGE_RK, MERGE_LDS };
+struct MergeLaunch {
+  MergePath path;
+  dim3 grid;
+  size_t lds;
+};
+static MergeLaunch merge_launch(int64_t nq, int k, int64_t C,
+                                MergePath first = MERGE_WAVE) {
+  if (first == MERGE_WAVE && merge_wave_ok(k, C))
+    return {MERGE_WAVE, dim3((unsigned)((nq + 3) / 4)), 0};
+  if (first <= MERGE_RK && use_regsel(k))
+    return {MERGE_RK, dim3((unsigned)nq), REGSEL_LDS_BYTES + 128};
+  return {MERGE_LDS, dim3((unsigned)nq), SEL_LDS_BYTES};
+}
+
 static dim3 grid1d(int64_t total, int block = 256, int64_t cap = 65535LL * 8) {
   int64_t g = (total + block - 1) / block;
   if (g > cap) g = cap;
@@ -1831,34 +1850,25 @@ static void launch_topk_rows(hipStream_t stream, unsigned bs_rk,
 }
 
 // Merge C candidates per query into the final top-k (D, I). ids maps
-// positions to ids (nullptr: positions are the ids). wave_ok lets the
-// wave-per-query kernel take the shapes merge_wave_ok admits.
+// positions to ids (nullptr: positions are the ids). first: see
+// merge_launch.
 static void launch_merge_cand(hipStream_t stream, const float *cand_d,
                               const unsigned *cand_p, int64_t nq, int C, int k,
                               const int64_t *ids, bool ip, float *D,
-                              int64_t *I, bool wave_ok) {
-  if (wave_ok && merge_wave_ok(k, C)) {
-    hipLaunchKernelGGL(k_merge_cand_w, dim3((unsigned)((nq + 3) / 4)),
-                       dim3(256), 0, stream, cand_d, cand_p, nq, C, k, ids,
-                       ip ? 1 : 0, D, I);
-  } else if (use_regsel(k)) {
-    hipLaunchKernelGGL(k_merge_cand_rk, dim3((unsigned)nq), dim3(256),
-                       REGSEL_LDS_BYTES + 128, stream, cand_d, cand_p, nq, C,
-                       k, ids, ip ? 1 : 0, D, I);
-  } else {
-    hipLaunchKernelGGL(k_merge_cand, dim3((unsigned)nq), dim3(256),
-                       SEL_LDS_BYTES, stream, cand_d, cand_p, nq, C, k, ids,
-                       ip ? 1 : 0, D, I);
-  }
+                              int64_t *I, MergePath first) {
+  const MergeLaunch m = merge_launch(nq, k, C, first);
+  auto kern = m.path == MERGE_WAVE ? k_merge_cand_w
+              : m.path == MERGE_RK ? k_merge_cand_rk
+                                   : k_merge_cand;
+  hipLaunchKernelGGL(kern, m.grid, dim3(256), m.lds, stream, cand_d, cand_p,
+                     nq, C, k, ids, ip ? 1 : 0, D, I);
 }
 
 static void pad_fill(dfann_index *h, int64_t nq, int k, float *D, int64_t *I,
                      hipStream_t stream) {
-  // empty index: all pads — run the merge kernel on zero candidates
-  hipLaunchKernelGGL(k_merge_cand, dim3((unsigned)nq), dim3(256), SEL_LDS_BYTES,
-                     stream, (const float *)nullptr, (const unsigned *)nullptr,
-                     nq, 0, k, (const int64_t *)nullptr,
-                     h->metric == M_IP ? 1 : 0, D, I);
+  // empty index: all pads — the LDS merge kernel on zero candidates
+  launch_merge_cand(stream, nullptr, nullptr, nq, 0, k, nullptr,
+                    h->metric == M_IP, D, I, MERGE_LDS);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2286,7 +2296,7 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
   TimingEv em;
   if (h->timing) em = h->ev_begin(stream);
   launch_merge_cand(stream, cand_d, cand_p, nq, nprobe * fan * k, k,
-                    h->cr_ids.as<int64_t>(), ip, D, I, true);
+                    h->cr_ids.as<int64_t>(), ip, D, I, MERGE_WAVE);
   if (h->timing) h->ev_end(em, stream, h->ev_merge);
   HIP_CHECK(hipGetLastError());
 }
@@ -2460,9 +2470,10 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
     }
   }
   // merge chunk winners (flat ids are positions: no id table; block-per-
-  // query kernels only)
+  // query kernels only: MERGE_RK excludes just the wave path, k > 16 still
+  // goes to the LDS kernel)
   launch_merge_cand(stream, wd, wp, nq, (int)(nch * k), k, nullptr, ip, D, I,
-                    false);
+                    MERGE_RK);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -3152,19 +3163,12 @@ extern "C" int dfann_merge_topk(int64_t nq, int S, int k, const float *D_dev,
   API_BEGIN
   (void)I_dev;  // slots map to metadata host-side (ref client.py:297-298)
   if (k > 512) throw std::runtime_error("k > 512 unsupported");
-  if (merge_wave_ok(k, (int64_t)S * k)) {
-    hipLaunchKernelGGL(k_merge_shards_w, dim3((unsigned)((nq + 3) / 4)),
-                       dim3(256), 0, (hipStream_t)stream, D_dev, nq, S, k,
-                       maximize, Dout_dev, Iout_dev);
-  } else if (use_regsel(k)) {
-    hipLaunchKernelGGL(k_merge_shards_rk, dim3((unsigned)nq), dim3(256),
-                       REGSEL_LDS_BYTES + 128, (hipStream_t)stream, D_dev, nq,
-                       S, k, maximize, Dout_dev, Iout_dev);
-  } else {
-    hipLaunchKernelGGL(k_merge_shards, dim3((unsigned)nq), dim3(256),
-                       SEL_LDS_BYTES, (hipStream_t)stream, D_dev, nq, S, k,
-                       maximize, Dout_dev, Iout_dev);
-  }
+  const MergeLaunch m = merge_launch(nq, k, (int64_t)S * k);
+  auto kern = m.path == MERGE_WAVE ? k_merge_shards_w
+              : m.path == MERGE_RK ? k_merge_shards_rk
+                                   : k_merge_shards;
+  hipLaunchKernelGGL(kern, m.grid, dim3(256), m.lds, (hipStream_t)stream,
+                     D_dev, nq, S, k, maximize, Dout_dev, Iout_dev);
   HIP_CHECK(hipGetLastError());
   API_END
 }

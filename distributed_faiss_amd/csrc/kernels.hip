@@ -366,6 +366,24 @@ extern "C" __global__ void k_f32_to_bf16(const float *__restrict__ in,
 #define GB_T 128
 #define GB_K 64
 
+// Store epilogue of the four bf16 GEMM kernels below: the wave's
+// acc[TI][4], its tile at (bi + wr, bj + wc) of C, goes out through
+// gemm_key (C/D fragment map above). A macro for the same reason as the
+// GLDS_* ones further down; #undef-ed with them after the last kernel.
+#define GEMM_BF16_STORE_KEYS(TI)                                               \
+  int rrow = (lane >> 4) * 4;                                                  \
+  _Pragma("unroll") for (int ti = 0; ti < TI; ++ti) {                          \
+    _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                         \
+      _Pragma("unroll") for (int rg = 0; rg < 4; ++rg) {                       \
+        int row = bi + wr + ti * 16 + rrow + rg;                               \
+        int col = bj + wc + tj * 16 + li;                                      \
+        if (row < M && col < N)                                                \
+          C[(size_t)row * ldc + col] =                                         \
+              gemm_key(acc[ti][tj][rg], row, col, qn, bn, mode);               \
+      }                                                                        \
+    }                                                                          \
+  }
+
 // Double-buffered, T14-scheduled (cdna_hip_programming.md §5.5 T14 /
 // Guideline 15): tile t+1's global loads are ISSUED before tile t's MFMA
 // phase and their LDS write lands after, behind the other buffer — HBM
@@ -460,50 +478,46 @@ extern "C" __global__ __launch_bounds__(256) void k_gemm_bf16_nt(
   }
   GB_MFMA(cur)
 
-  int rrow = (lane >> 4) * 4;
-#pragma unroll
-  for (int ti = 0; ti < 4; ++ti) {
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        int row = bi + wr + ti * 16 + rrow + rg;
-        int col = bj + wc + tj * 16 + li;
-        if (row < M && col < N)
-          C[(size_t)row * ldc + col] =
-              gemm_key(acc[ti][tj][rg], row, col, qn, bn, mode);
-      }
-    }
-  }
+  GEMM_BF16_STORE_KEYS(4)
 #undef GB_LOAD
 #undef GB_WRITE
 #undef GB_MFMA
 }
 
-// glds-staged variant (cdna_hip_programming.md §5 ladder step 3 /
+// ---------------------------------------------------------------------------
+// glds-staged bf16 GEMMs (cdna_hip_programming.md §5 ladder step 3 /
 // Guideline 15): global->LDS DMA (16-B wide) stages the next tile while
 // the MFMAs run; ONE __shared__ object (a second one de-pipelines glds —
 // §5 ".s-level traps" (a)); LDS image is lane-linear, so the bank
 // swizzle lives on the SOURCE address and the fragment-read offset
 // (rule 21): byte ^= (row&7)<<4 cuts the 16-lane ds_read_b128 group from
-// 8-way to 2-way. Requires K % 8 == 0 (host falls back otherwise).
-extern "C" __global__ __launch_bounds__(256) void k_gemm_bf16_glds(
-    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
-    float *__restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
-    const float *__restrict__ qn, const float *__restrict__ bn, int mode) {
-  // [buf][operand][row][col] bf16, linear (swizzle on source/read)
-  __shared__ unsigned short smem2[2][2][GB_T][GB_K];
-  int bi = blockIdx.y * GB_T;
-  int bj = blockIdx.x * GB_T;
-  int tid = threadIdx.x;
-  int lane = tid & 63, w = tid >> 6;
-  int wr = (w >> 1) * 64, wc = (w & 1) * 64;
-  f32x4 acc[4][4] = {};
-  int li = lane & 15;
+// 8-way to 2-way. Requires K % 8 == 0 (host falls back otherwise); ragged
+// M/N/K are handled by the stage guards (out-of-range positions stage
+// zeros).
+//
+// The GLDS_* macros below are the one copy of the stage, the MFMA step and
+// the double-buffered main loop, for a square tile of edge TILE = 128 or
+// 256: TILE/32 waves as 2(M) x TILE/64(N), wave tile (TILE/2) x 64, acc
+// [TILE/32][4] f32x4. They are macros, not function templates, because
+// the template form changed the register allocation of all three kernels
+// (profiles/select_gemm); they are #undef-ed after the last kernel.
+// ---------------------------------------------------------------------------
+
+// [buf][operand][row][col] bf16, linear (swizzle on source/read)
+#define GLDS_SETUP(TILE)                                                       \
+  __shared__ unsigned short smem2[2][2][TILE][GB_K];                           \
+  int bi = blockIdx.y * TILE;                                                  \
+  int bj = blockIdx.x * TILE;                                                  \
+  int tid = threadIdx.x;                                                       \
+  int lane = tid & 63, w = tid >> 6;                                           \
+  int wr = (w / (TILE / 64)) * (TILE / 2), wc = (w % (TILE / 64)) * 64;        \
+  f32x4 acc[TILE / 32][4] = {};                                                \
+  int li = lane & 15;                                                          \
   int ke = (lane >> 4) * 8;
 
-  // wave w stages rows [w*32, w*32+32) of each operand: 4 glds per operand,
-  // each covering 64 consecutive 16-B groups (8 rows)
+// wave w stages rows [w*32, w*32+32) of each operand: 4 glds per operand,
+// each covering 64 consecutive 16-B groups (8 rows); TILE*8 groups per
+// operand = TILE/32 waves x 4 glds x 64 lanes
 #define GLDS_STAGE(BUF, K0)                                                    \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                              \
     int g = (w * 4 + i) * 64 + lane; /* group index, lane-linear */            \
@@ -534,17 +548,16 @@ extern "C" __global__ __launch_bounds__(256) void k_gemm_bf16_glds(
           &smem2[BUF][1][0][0] + (size_t)g * 8) = uint4{0, 0, 0, 0};           \
   }
 
-#define GLDS_MFMA(BUF)                                                         \
+#define GLDS_MFMA(TILE, BUF)                                                   \
   _Pragma("unroll") for (int kk = 0; kk < GB_K; kk += 32) {                    \
-    _Pragma("unroll") for (int ti = 0; ti < 4; ++ti) {                         \
-      int ra = wr + ti * 16 + li;                                              \
-      int ca = (kk + ke) ^ ((ra & 7) << 3);                                    \
-      bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(&smem2[BUF][0][ra][ca]);   \
-      _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                       \
-        int rb = wc + tj * 16 + li;                                            \
-        int cbx = (kk + ke) ^ ((rb & 7) << 3);                                 \
-        bf16x8 b0 =                                                            \
-            *reinterpret_cast<const bf16x8 *>(&smem2[BUF][1][rb][cbx]);        \
+    _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                         \
+      int rb = wc + tj * 16 + li;                                              \
+      int cbx = (kk + ke) ^ ((rb & 7) << 3);                                   \
+      bf16x8 b0 = *reinterpret_cast<const bf16x8 *>(&smem2[BUF][1][rb][cbx]);  \
+      _Pragma("unroll") for (int ti = 0; ti < TILE / 32; ++ti) {               \
+        int ra = wr + ti * 16 + li;                                            \
+        int ca = (kk + ke) ^ ((ra & 7) << 3);                                  \
+        bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(&smem2[BUF][0][ra][ca]); \
         acc[ti][tj] =                                                          \
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[ti][tj],       \
                                                     0, 0, 0);                  \
@@ -552,35 +565,140 @@ extern "C" __global__ __launch_bounds__(256) void k_gemm_bf16_glds(
     }                                                                          \
   }
 
-  GLDS_STAGE(0, 0)
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = GB_K; k0 < K; k0 += GB_K) {
-    GLDS_STAGE(cur ^ 1, k0)  // DMA in flight during the MFMAs
-    GLDS_MFMA(cur)
-    __syncthreads();  // drains the glds queue (vmcnt(0) inside)
-    cur ^= 1;
-  }
-  GLDS_MFMA(cur)
+#define GLDS_MAINLOOP(TILE)                                                    \
+  GLDS_STAGE(0, 0)                                                             \
+  __syncthreads();                                                             \
+  int cur = 0;                                                                 \
+  for (int k0 = GB_K; k0 < K; k0 += GB_K) {                                    \
+    GLDS_STAGE(cur ^ 1, k0) /* DMA in flight during the MFMAs */               \
+    GLDS_MFMA(TILE, cur)                                                       \
+    __syncthreads(); /* drains the glds queue (vmcnt(0) inside) */             \
+    cur ^= 1;                                                                  \
+  }                                                                            \
+  GLDS_MFMA(TILE, cur)
 
+// 128^2 tile, 4 waves: every K % 8 == 0 shape the 256^2 kernel does not
+// take
+extern "C" __global__ __launch_bounds__(256) void k_gemm_bf16_glds(
+    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
+    float *__restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
+    const float *__restrict__ qn, const float *__restrict__ bn, int mode) {
+  GLDS_SETUP(GB_T)
+  GLDS_MAINLOOP(GB_T)
+  GEMM_BF16_STORE_KEYS(4)
+}
+
+// 256^2 tile, 8 waves (cdna_hip_programming.md §5 glds table: 256² BK=64
+// 2-buffer glds is the top tier for large GEMMs — the 128² tile peaks
+// ~620 TF, this shape ~1.2 PF). Used for the big coarse/assign GEMMs
+// (N = nlist >= 2048).
+extern "C" __global__ __launch_bounds__(512) void k_gemm_bf16_256(
+    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
+    float *__restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
+    const float *__restrict__ qn, const float *__restrict__ bn, int mode) {
+  GLDS_SETUP(256)
+  GLDS_MAINLOOP(256)
+  GEMM_BF16_STORE_KEYS(8)
+}
+
+// ---------------------------------------------------------------------------
+// k_gemm_bf16_256 with the coarse select fused into the epilogue: same
+// staging, swizzle, MFMA loop and accumulator layout (GLDS_SETUP and
+// GLDS_MAINLOOP), same gemm_key() on the same accumulators — but C is never
+// stored. Each block reduces its 256x256 key tile to the NP smallest
+// (key, col) pairs per row (sel_less order) and writes them to a
+// candidate buffer laid out (row, n_tile, NP); k_coarse_reduce_rk picks
+// the final nprobe. Slots without a valid column stay (FLT_MAX, PAD_POS);
+// rows >= M write nothing.
+//
+// Epilogue: the 128 KB operand buffer is reused as a 256x128 fp32 tile,
+// filled in two passes (tj 0-1, then tj 2-3, so all 8 waves store in
+// both). Thread t owns row t>>1, 64-column chunk t&1, and streams it
+// through a RegTopK<NP> with ds_read_b128; the start slot is rotated by
+// t so the 16 lanes of a read group (distinct t mod 16) hit 16 distinct
+// 16-B slots of the 256-B bank row. Push order does not matter: (key,
+// col) is a strict total order. The two threads of a row then exchange
+// their lists by shuffle.
+// ---------------------------------------------------------------------------
+template <int NP>
+__global__ __launch_bounds__(512) void k_gemm_bf16_256_topk(
+    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
+    int M, int N, int K, int lda, int ldb, const float *__restrict__ qn,
+    const float *__restrict__ bn, int mode, float *__restrict__ cand_d,
+    unsigned *__restrict__ cand_p) {
+  GLDS_SETUP(256)
+  GLDS_MAINLOOP(256)
+  __syncthreads();  // every wave is done with the operand tiles
+
+  float *tile = reinterpret_cast<float *>(&smem2[0][0][0][0]);  // [256][128]
   int rrow = (lane >> 4) * 4;
+  int srow = tid >> 1, sch = tid & 1;
+  int grow = bi + srow;
+  RegTopK<NP> loc;
+  loc.init();
 #pragma unroll
-  for (int ti = 0; ti < 4; ++ti) {
+  for (int hf = 0; hf < 2; ++hf) {
+    if (hf) __syncthreads();  // first half consumed
 #pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
+    for (int ti = 0; ti < 8; ++ti) {
 #pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        int row = bi + wr + ti * 16 + rrow + rg;
-        int col = bj + wc + tj * 16 + li;
-        if (row < M && col < N)
-          C[(size_t)row * ldc + col] =
-              gemm_key(acc[ti][tj][rg], row, col, qn, bn, mode);
+      for (int tjl = 0; tjl < 2; ++tjl) {
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          int lrow = wr + ti * 16 + rrow + rg;
+          int row = bi + lrow;
+          int col = bj + wc + (hf * 2 + tjl) * 16 + li;
+          float key = DFANN_FLT_MAX;
+          if (row < M && col < N)
+            key = gemm_key(acc[ti][hf * 2 + tjl][rg], row, col, qn, bn, mode);
+          tile[lrow * 128 + (w & 3) * 32 + tjl * 16 + li] = key;
+        }
+      }
+    }
+    __syncthreads();
+    const float4 *rp =
+        reinterpret_cast<const float4 *>(tile + srow * 128 + sch * 64);
+#pragma unroll 4
+    for (int j = 0; j < 16; ++j) {
+      int s = (j + tid) & 15;
+      float4 v = rp[s];
+      // tile column -> global column (4 consecutive share a 16-col group)
+      int lc = sch * 64 + s * 4;
+      int col = bj + (lc >> 5) * 64 + (hf * 2 + ((lc >> 4) & 1)) * 16 +
+                (lc & 15);
+      if (grow < M) {
+        if (col + 0 < N) loc.push(v.x, (unsigned)(col + 0));
+        if (col + 1 < N) loc.push(v.y, (unsigned)(col + 1));
+        if (col + 2 < N) loc.push(v.z, (unsigned)(col + 2));
+        if (col + 3 < N) loc.push(v.w, (unsigned)(col + 3));
       }
     }
   }
+  // merge the row's two 64-column chunks (lanes t, t^1)
+  float od[NP];
+  unsigned op[NP];
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    od[i] = __shfl_xor(loc.d[i], 1, 64);
+    op[i] = __shfl_xor(loc.p[i], 1, 64);
+  }
+#pragma unroll
+  for (int i = 0; i < NP; ++i) loc.push(od[i], op[i]);
+  if (sch == 0 && grow < M) {
+    size_t o = ((size_t)grow * gridDim.x + blockIdx.x) * NP;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      cand_d[o + i] = loc.d[i];
+      cand_p[o + i] = loc.p[i];
+    }
+  }
+}
+
+#undef GEMM_BF16_STORE_KEYS
+#undef GLDS_SETUP
 #undef GLDS_STAGE
 #undef GLDS_MFMA
-}
+#undef GLDS_MAINLOOP
 
 // ---------------------------------------------------------------------------
 // row norms ||x_i||^2, one block per row
@@ -770,219 +888,6 @@ extern "C" __global__ __launch_bounds__(256) void k_topk_rows_rk_f(
                           allow);
 }
 
-// ---------------------------------------------------------------------------
-// running argmin across key-matrix chunks (assignment). rows = points.
-// best_v/best_i persist across chunk calls (init by k_fill_assign_init).
-// Ties: lowest global column (chunks ascending, strict <).
-// 256^2-tile variant (cdna_hip_programming.md §5 glds table: 256² BK=64
-// 2-buffer glds is the top tier for large GEMMs — the 128² tile peaks
-// ~620 TF, this shape ~1.2 PF): 512 threads = 8 waves as 2(M)x4(N),
-// wave tile 128x64, acc 8x4 f32x4. Same source-XOR swizzle + lane-linear
-// LDS + single __shared__ as k_gemm_bf16_glds. Used for the big
-// coarse/assign GEMMs (N = nlist >= 2048); ragged M/N/K handled by the
-// stage guards (out-of-range positions stage zeros).
-#define GB2_T 256
-extern "C" __global__ __launch_bounds__(512) void k_gemm_bf16_256(
-    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
-    float *__restrict__ C, int M, int N, int K, int lda, int ldb, int ldc,
-    const float *__restrict__ qn, const float *__restrict__ bn, int mode) {
-  __shared__ unsigned short smem2[2][2][GB2_T][GB_K];
-  int bi = blockIdx.y * GB2_T;
-  int bj = blockIdx.x * GB2_T;
-  int tid = threadIdx.x;
-  int lane = tid & 63, w = tid >> 6;
-  int wr = (w >> 2) * 128, wc = (w & 3) * 64;
-  f32x4 acc[8][4] = {};
-  int li = lane & 15;
-  int ke = (lane >> 4) * 8;
-
-  // 2048 16-B groups per operand, 8 waves x 4 glds x 64 lanes
-#define GLDS2_STAGE(BUF, K0)                                                   \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                              \
-    int g = (w * 4 + i) * 64 + lane;                                           \
-    int r = g >> 3;                                                            \
-    int c8 = (g & 7) * 8;                                                      \
-    int c8s = c8 ^ ((r & 7) << 3);                                             \
-    unsigned short *ldst = &smem2[BUF][0][0][0] + ((size_t)(w * 4 + i) * 64) * 8; \
-    const unsigned short *ga = &A[(size_t)(bi + r) * lda + (K0) + c8s];        \
-    const unsigned short *gb = &B[(size_t)(bj + r) * ldb + (K0) + c8s];        \
-    bool oka = (bi + r < M) && ((K0) + c8s + 7 < K);                           \
-    bool okb = (bj + r < N) && ((K0) + c8s + 7 < K);                           \
-    if (oka)                                                                   \
-      __builtin_amdgcn_global_load_lds(                                        \
-          (const __attribute__((address_space(1))) unsigned int *)ga,          \
-          (__attribute__((address_space(3))) unsigned int *)ldst, 16, 0, 0);   \
-    else                                                                       \
-      *reinterpret_cast<uint4 *>(                                              \
-          &smem2[BUF][0][0][0] + (size_t)g * 8) = uint4{0, 0, 0, 0};           \
-    unsigned short *ldstB = &smem2[BUF][1][0][0] + ((size_t)(w * 4 + i) * 64) * 8; \
-    if (okb)                                                                   \
-      __builtin_amdgcn_global_load_lds(                                        \
-          (const __attribute__((address_space(1))) unsigned int *)gb,          \
-          (__attribute__((address_space(3))) unsigned int *)ldstB, 16, 0, 0);  \
-    else                                                                       \
-      *reinterpret_cast<uint4 *>(                                              \
-          &smem2[BUF][1][0][0] + (size_t)g * 8) = uint4{0, 0, 0, 0};           \
-  }
-
-#define GLDS2_MFMA(BUF)                                                        \
-  _Pragma("unroll") for (int kk = 0; kk < GB_K; kk += 32) {                    \
-    _Pragma("unroll") for (int tj = 0; tj < 4; ++tj) {                         \
-      int rb = wc + tj * 16 + li;                                              \
-      int cbx = (kk + ke) ^ ((rb & 7) << 3);                                   \
-      bf16x8 b0 = *reinterpret_cast<const bf16x8 *>(&smem2[BUF][1][rb][cbx]);  \
-      _Pragma("unroll") for (int ti = 0; ti < 8; ++ti) {                       \
-        int ra = wr + ti * 16 + li;                                            \
-        int ca = (kk + ke) ^ ((ra & 7) << 3);                                  \
-        bf16x8 a0 = *reinterpret_cast<const bf16x8 *>(&smem2[BUF][0][ra][ca]); \
-        acc[ti][tj] =                                                          \
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[ti][tj],       \
-                                                    0, 0, 0);                  \
-      }                                                                        \
-    }                                                                          \
-  }
-
-  GLDS2_STAGE(0, 0)
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = GB_K; k0 < K; k0 += GB_K) {
-    GLDS2_STAGE(cur ^ 1, k0)
-    GLDS2_MFMA(cur)
-    __syncthreads();
-    cur ^= 1;
-  }
-  GLDS2_MFMA(cur)
-
-  int rrow = (lane >> 4) * 4;
-#pragma unroll
-  for (int ti = 0; ti < 8; ++ti) {
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        int row = bi + wr + ti * 16 + rrow + rg;
-        int col = bj + wc + tj * 16 + li;
-        if (row < M && col < N)
-          C[(size_t)row * ldc + col] =
-              gemm_key(acc[ti][tj][rg], row, col, qn, bn, mode);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// k_gemm_bf16_256 with the coarse select fused into the epilogue: same
-// staging, swizzle, MFMA loop and accumulator layout (the GLDS2_* macros
-// above, left defined for it), same gemm_key() on the same accumulators — but C is never
-// stored. Each block reduces its 256x256 key tile to the NP smallest
-// (key, col) pairs per row (sel_less order) and writes them to a
-// candidate buffer laid out (row, n_tile, NP); k_coarse_reduce_rk picks
-// the final nprobe. Slots without a valid column stay (FLT_MAX, PAD_POS);
-// rows >= M write nothing.
-//
-// Epilogue: the 128 KB operand buffer is reused as a 256x128 fp32 tile,
-// filled in two passes (tj 0-1, then tj 2-3, so all 8 waves store in
-// both). Thread t owns row t>>1, 64-column chunk t&1, and streams it
-// through a RegTopK<NP> with ds_read_b128; the start slot is rotated by
-// t so the 16 lanes of a read group (distinct t mod 16) hit 16 distinct
-// 16-B slots of the 256-B bank row. Push order does not matter: (key,
-// col) is a strict total order. The two threads of a row then exchange
-// their lists by shuffle.
-// ---------------------------------------------------------------------------
-template <int NP>
-__global__ __launch_bounds__(512) void k_gemm_bf16_256_topk(
-    const unsigned short *__restrict__ A, const unsigned short *__restrict__ B,
-    int M, int N, int K, int lda, int ldb, const float *__restrict__ qn,
-    const float *__restrict__ bn, int mode, float *__restrict__ cand_d,
-    unsigned *__restrict__ cand_p) {
-  __shared__ unsigned short smem2[2][2][GB2_T][GB_K];
-  int bi = blockIdx.y * GB2_T;
-  int bj = blockIdx.x * GB2_T;
-  int tid = threadIdx.x;
-  int lane = tid & 63, w = tid >> 6;
-  int wr = (w >> 2) * 128, wc = (w & 3) * 64;
-  f32x4 acc[8][4] = {};
-  int li = lane & 15;
-  int ke = (lane >> 4) * 8;
-
-  GLDS2_STAGE(0, 0)
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = GB_K; k0 < K; k0 += GB_K) {
-    GLDS2_STAGE(cur ^ 1, k0)
-    GLDS2_MFMA(cur)
-    __syncthreads();
-    cur ^= 1;
-  }
-  GLDS2_MFMA(cur)
-  __syncthreads();  // every wave is done with the operand tiles
-
-  float *tile = reinterpret_cast<float *>(&smem2[0][0][0][0]);  // [256][128]
-  int rrow = (lane >> 4) * 4;
-  int srow = tid >> 1, sch = tid & 1;
-  int grow = bi + srow;
-  RegTopK<NP> loc;
-  loc.init();
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    if (hf) __syncthreads();  // first half consumed
-#pragma unroll
-    for (int ti = 0; ti < 8; ++ti) {
-#pragma unroll
-      for (int tjl = 0; tjl < 2; ++tjl) {
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          int lrow = wr + ti * 16 + rrow + rg;
-          int row = bi + lrow;
-          int col = bj + wc + (hf * 2 + tjl) * 16 + li;
-          float key = DFANN_FLT_MAX;
-          if (row < M && col < N)
-            key = gemm_key(acc[ti][hf * 2 + tjl][rg], row, col, qn, bn, mode);
-          tile[lrow * 128 + (w & 3) * 32 + tjl * 16 + li] = key;
-        }
-      }
-    }
-    __syncthreads();
-    const float4 *rp =
-        reinterpret_cast<const float4 *>(tile + srow * 128 + sch * 64);
-#pragma unroll 4
-    for (int j = 0; j < 16; ++j) {
-      int s = (j + tid) & 15;
-      float4 v = rp[s];
-      // tile column -> global column (4 consecutive share a 16-col group)
-      int lc = sch * 64 + s * 4;
-      int col = bj + (lc >> 5) * 64 + (hf * 2 + ((lc >> 4) & 1)) * 16 +
-                (lc & 15);
-      if (grow < M) {
-        if (col + 0 < N) loc.push(v.x, (unsigned)(col + 0));
-        if (col + 1 < N) loc.push(v.y, (unsigned)(col + 1));
-        if (col + 2 < N) loc.push(v.z, (unsigned)(col + 2));
-        if (col + 3 < N) loc.push(v.w, (unsigned)(col + 3));
-      }
-    }
-  }
-  // merge the row's two 64-column chunks (lanes t, t^1)
-  float od[NP];
-  unsigned op[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    od[i] = __shfl_xor(loc.d[i], 1, 64);
-    op[i] = __shfl_xor(loc.p[i], 1, 64);
-  }
-#pragma unroll
-  for (int i = 0; i < NP; ++i) loc.push(od[i], op[i]);
-  if (sch == 0 && grow < M) {
-    size_t o = ((size_t)grow * gridDim.x + blockIdx.x) * NP;
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      cand_d[o + i] = loc.d[i];
-      cand_p[o + i] = loc.p[i];
-    }
-  }
-#undef GLDS2_STAGE
-#undef GLDS2_MFMA
-}
-
 // second stage of the fused coarse select: per query row, the top k of
 // the ncand = n_tile * NP candidates by (key, pos); pads are skipped.
 // Output layout as k_topk_rows_rk with ldo = k. blockDim: 64..256.
@@ -1005,6 +910,10 @@ extern "C" __global__ __launch_bounds__(256) void k_coarse_reduce_rk(
   regtopk_block_extract<16>(loc, k, smem, out_d + row * k, out_p + row * k);
 }
 
+// ---------------------------------------------------------------------------
+// running argmin across key-matrix chunks (assignment). rows = points.
+// best_v/best_i persist across chunk calls (init by k_assign_init).
+// Ties: lowest global column (chunks ascending, strict <).
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ void k_assign_init(float *best_v, int *best_i, long long n) {
@@ -3295,7 +3204,7 @@ __device__ __forceinline__ float refine_acc(float part, const float *xv,
 // One 256-thread block per query; 16 lanes per candidate row, 16 rows per
 // pass. Lane g of a row owns the 8-element chunks at t0 = 8g, 8g+128, ...
 // and sums them in ascending t; the 16 partials meet in an xor butterfly
-// (8, 4, 2, 1). That order IS the numeric contract (tests/refine_ref.py
+// (8, 4, 2, 1). That order IS the numeric contract (oracle/refine.py
 // restates it op for op). Selection: (key, ascending id) through a
 // monotone uint encoding of the minimize key (L2 distance / -dot), packed
 // with the id into one u64 and bitonic-sorted in LDS; candidates that are
