@@ -1375,6 +1375,10 @@ static void encode_chunk(dfann_index *h, int64_t n, const float *x,
   h->pend_arena.ensure_rows(row0 + n);
   uint8_t *const *dst = h->pend_arena.dev_table_mut(stream);
   int rlog = h->pend_arena.rlog;
+  if (h->stride > h->code_bytes)
+    hipLaunchKernelGGL(k_zero_row_pad,
+                       grid1d(n * (h->stride - h->code_bytes)), dim3(256), 0,
+                       stream, n, h->code_bytes, h->stride, rlog, row0, dst);
   if (h->type == T_IVFFLAT) {
     hipLaunchKernelGGL(k_pack_rows, grid1d(n * h->d), dim3(256), 0, stream, x,
                        n, h->d, h->stride, rlog, row0, dst);

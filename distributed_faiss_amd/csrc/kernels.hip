@@ -2732,6 +2732,19 @@ extern "C" __global__ void k_pack_rows(const float *__restrict__ x, long long n,
   }
 }
 
+// zero bytes [code_bytes, stride) of rows [row0, row0+n): a fresh slab holds
+// whatever the allocator hands out, and the pad travels with the row
+// (rebuild gather, get_lists, save), so the encoders' rows get it written
+extern "C" __global__ void k_zero_row_pad(long long n, int code_bytes,
+                                          int stride, int rlog, long long row0,
+                                          uint8_t *const *__restrict__ out) {
+  const int pad = stride - code_bytes;
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = n * pad;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x)
+    slab_row_mut(out, rlog, row0 + i / pad, stride)[code_bytes + i % pad] = 0;
+}
+
 // two-source CSR rebuild gather (DESIGN.md §2 memory plan): new CSR row j
 // of list l is either an OLD CSR row (same list order) or a PENDING row
 // (arrival order within the list, via the psrc permutation). Both source

@@ -196,6 +196,15 @@ def test_lists_equal_masked_dump(kind, name):
     _assert_lists(eng, _masked_dump(dump, removed))
 
 
+@pytest.mark.parametrize("kind,code_bytes", [("pq8", 8), ("pq4", 4), ("opq", 8)])
+def test_pad_bytes_are_zero(kind, code_bytes):
+    """The byte-for-byte comparisons of this file take in the pad of a row
+    (stride 16 here), which add has to write: a fresh slab is not cleared."""
+    codes = _twin(kind)[1][2]
+    assert codes.shape == (N, 16)
+    assert not codes[:, code_bytes:].any()
+
+
 @pytest.mark.parametrize("how", ["ids", "packed"])
 def test_remove_while_rows_are_pending(how):
     """An add with no search before the removal: pending rows are merged in
