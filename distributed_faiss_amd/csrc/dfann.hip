@@ -355,8 +355,13 @@ struct dfann_index {
   std::vector<int32_t> h_levels, h_upslot;
   DevBuf hn_levels, hn_nbr0, hn_cnt0, hn_upslot, hn_nbrU, hn_cntU;
   DevBuf hn_req, hn_reqcnt, hn_runoff, hn_u;
-  // flat arena
+  // flat arena: fp32 rows of d floats, or with spec "flat_store": "fp16"
+  //  fp16 rows of flat_ldh = round_up(d, 8) halves, zero pad,
+  // and for L2 their ||x||^2 (fp32, of the rounded values) in flat_norm
   DevBuf flat;
+  bool flat_f16 = false;
+  int flat_ldh = 0;
+  DevBuf flat_norm;
   // workspace
   DevBuf ws1, ws2, ws3, ws4, ws5, ws_bf16a, ws_bf16b;
   DevBuf cent_bf16;
@@ -454,6 +459,32 @@ static MergeLaunch merge_launch(int64_t nq, int k, int64_t C,
   if (first <= MERGE_RK && use_regsel(k))
     return {MERGE_RK, dim3((unsigned)nq), REGSEL_LDS_BYTES + 128};
   return {MERGE_LDS, dim3((unsigned)nq), SEL_LDS_BYTES};
+}
+
+// Launch shape of the fused flat fp16 search (k_flat_f16):
+// grid = (database splits S, query tiles), a block walking its split's
+// tiles. A block takes a whole CU (96 KB LDS), so with few query tiles S
+// makes the grid cover the CUs about twice — the second round evens out the
+// ragged end of the first — and from 2 x CUs query tiles on S = 1: each
+// further split only adds candidates to merge. Returns the tiles per
+// split; S = ceil(ntiles / that), so no split is empty.
+// DFANN_FLAT_SPLITS=<n> (A/B knob, read per call) overrides S.
+static int64_t flat_tiles_per_split(int64_t qtiles, int64_t ntiles) {
+  int64_t S = 0;
+  if (const char *e = getenv("DFANN_FLAT_SPLITS")) S = atoll(e);
+  if (S < 1) {
+    static int cus = 0;
+    if (!cus) {
+      int dev = 0;
+      HIP_CHECK(hipGetDevice(&dev));
+      HIP_CHECK(hipDeviceGetAttribute(
+          &cus, hipDeviceAttributeMultiprocessorCount, dev));
+      if (cus < 1) cus = 1;
+    }
+    S = (2 * cus + qtiles - 1) / qtiles;
+  }
+  S = std::min(std::max<int64_t>(S, 1), ntiles);
+  return (ntiles + S - 1) / S;
 }
 
 static dim3 grid1d(int64_t total, int block = 256, int64_t cap = 65535LL * 8) {
@@ -1051,6 +1082,19 @@ static dfann_index *create_from_spec(const std::string &js) {
     delete h;
     throw std::runtime_error("opq_dim given without \"opq\": 1");
   }
+  {
+    std::string fs;
+    if (json_find(js, "flat_store", fs)) {
+      std::string bad;
+      if (h->type != T_FLAT)
+        bad = "\"flat_store\" unsupported for index type '" + t +
+              "' (flat only)";
+      else if (fs != "fp32" && fs != "fp16")
+        bad = "flat_store='" + fs + "' unsupported (supported: fp32, fp16)";
+      if (!bad.empty()) { delete h; throw std::runtime_error(bad); }
+      h->flat_f16 = fs == "fp16";
+    }
+  }
   if (h->type != T_FLAT && h->type != T_HNSW && h->nlist <= 0) {
     delete h;
     throw std::runtime_error("bad nlist");
@@ -1111,7 +1155,8 @@ static dfann_index *create_from_spec(const std::string &js) {
     h->sq_bits = 8;
     h->code_bytes = h->d;
   } else {
-    h->code_bytes = 4 * h->d;
+    h->flat_ldh = (h->d + 7) & ~7;
+    h->code_bytes = h->flat_f16 ? 2 * h->flat_ldh : 4 * h->d;
     h->trained = true;  // flat needs no training
   }
   h->stride = round16(h->code_bytes);
@@ -1488,6 +1533,23 @@ static void flat_live_extend(dfann_index *h, int64_t from) {
                         hipMemcpyHostToDevice));
 }
 
+// flat fp16: (n x d) fp32 rows -> fp16 rows of ldh halves
+// with zero pad; ||row||^2 of n stored rows. Add, load and the per-call
+// query conversion all go through these two.
+static void flat_f16_rows(const float *x, int64_t n, int d, int ldh,
+                          unsigned short *out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_flat_f16_store, grid1d(n * ldh), dim3(256), 0, stream,
+                     x, (long long)n, d, ldh, out);
+  HIP_CHECK(hipGetLastError());
+}
+static void flat_f16_norms(const unsigned short *rows, int64_t n, int ldh,
+                           float *out, hipStream_t stream) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_flat_f16_norm, dim3((unsigned)((n + 3) / 4)), dim3(256),
+                     0, stream, rows, (long long)n, ldh, out);
+  HIP_CHECK(hipGetLastError());
+}
+
 static void add_impl(dfann_index *h, int64_t n, const float *x,
                      hipStream_t stream) {
   if (!h->trained) throw std::runtime_error("add on untrained index");
@@ -1495,11 +1557,28 @@ static void add_impl(dfann_index *h, int64_t n, const float *x,
   if (h->opq) opq_require(h);
   if (h->type == T_HNSW) { hnsw_add(h, n, x, stream); return; }
   if (h->type == T_FLAT) {
-    h->flat.grow_keep(((size_t)h->ntotal + n) * h->d * 4,
-                      (size_t)h->ntotal * h->d * 4);
-    HIP_CHECK(hipMemcpyAsync(h->flat.as<float>() + (size_t)h->ntotal * h->d, x,
-                             (size_t)n * h->d * 4, hipMemcpyDeviceToDevice,
-                             stream));
+    if (h->flat_f16) {
+      if (h->ntotal + n > 0xFFFFFFFFLL)
+        throw std::runtime_error("add: flat positions are 32-bit");
+      const size_t ldh = (size_t)h->flat_ldh;
+      h->flat.grow_keep(((size_t)h->ntotal + n) * ldh * 2,
+                        (size_t)h->ntotal * ldh * 2);
+      unsigned short *rows =
+          h->flat.as<unsigned short>() + (size_t)h->ntotal * ldh;
+      flat_f16_rows(x, n, h->d, h->flat_ldh, rows, stream);
+      if (h->metric == M_L2) {
+        h->flat_norm.grow_keep(((size_t)h->ntotal + n) * 4,
+                               (size_t)h->ntotal * 4);
+        flat_f16_norms(rows, n, h->flat_ldh,
+                       h->flat_norm.as<float>() + h->ntotal, stream);
+      }
+    } else {
+      h->flat.grow_keep(((size_t)h->ntotal + n) * h->d * 4,
+                        (size_t)h->ntotal * h->d * 4);
+      HIP_CHECK(hipMemcpyAsync(h->flat.as<float>() + (size_t)h->ntotal * h->d,
+                               x, (size_t)n * h->d * 4,
+                               hipMemcpyDeviceToDevice, stream));
+    }
     HIP_CHECK(hipStreamSynchronize(stream));
     h->ntotal += n;
     if (h->nremoved) flat_live_extend(h, h->ntotal - n);
@@ -2420,6 +2499,72 @@ static void range_impl(dfann_index *h, int64_t nq, const float *q_dev,
   *I_out = h->range_I.as<int64_t>();
 }
 
+// flat fp16: one k_flat_f16 launch over query rows
+// [s, s + c) (converted, in ws_bf16a; norms in ws5) and database rows
+// [b0, b0 + rows). Counted in the gemm bucket.
+template <int KP, bool FILT, bool STORE>
+static void launch_flat_f16(dfann_index *h, dim3 g, int64_t s, int64_t c,
+                            int64_t b0, int64_t rows, int tiles_per_split,
+                            const uint32_t *allow, int k, float *cand_d,
+                            unsigned *cand_p, float *C, hipStream_t stream) {
+  const size_t ldh = (size_t)h->flat_ldh;
+  const bool ip = h->metric == M_IP;
+  TimingEv e;
+  if (h->timing) e = h->ev_begin(stream);
+  hipLaunchKernelGGL(
+      HIP_KERNEL_NAME(k_flat_f16<KP, FILT, STORE>), g, dim3(512), 0, stream,
+      h->ws_bf16a.as<unsigned short>() + (size_t)s * ldh,
+      h->flat.as<unsigned short>() + (size_t)b0 * ldh, (int)c,
+      (long long)rows, h->flat_ldh,
+      ip ? (const float *)nullptr : h->ws5.as<float>() + s,
+      ip ? (const float *)nullptr : h->flat_norm.as<float>() + b0, ip ? 0 : 2,
+      tiles_per_split, allow, k, cand_d, cand_p, C);
+  if (h->timing) {
+    h->ev_end(e, stream, h->ev_gemm);
+    h->gemm_flops += 2LL * c * rows * h->d;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// k > 16: the keys of one (query chunk, database chunk) into sc, for the
+// two-pass select of flat_search_impl
+static void flat_f16_keys(dfann_index *h, int64_t s, int64_t c, int64_t b0,
+                          int64_t rows, float *sc, hipStream_t stream) {
+  dim3 g((unsigned)((rows + FH_TN - 1) / FH_TN),
+         (unsigned)((c + FH_TM - 1) / FH_TM));
+  launch_flat_f16<1, false, true>(h, g, s, c, b0, rows, 1, nullptr, 0, nullptr,
+                                  nullptr, sc, stream);
+}
+
+// k <= 16: the whole search in one launch plus the candidate merge. No key
+// matrix: ws3 / ws4 hold nq * S * k candidate pairs.
+static void flat_f16_fused(dfann_index *h, int64_t nq, int k, float *D,
+                           int64_t *I, hipStream_t stream,
+                           const uint32_t *allow) {
+  const int64_t N = h->ntotal;
+  const int64_t qtiles = (nq + FH_TM - 1) / FH_TM;
+  const int64_t ntiles = (N + FH_TN - 1) / FH_TN;
+  const int tps = (int)flat_tiles_per_split(qtiles, ntiles);
+  const int64_t S = (ntiles + tps - 1) / tps;
+  h->ws3.ensure((size_t)nq * S * k * 4);
+  h->ws4.ensure((size_t)nq * S * k * 4);
+  float *wd = h->ws3.as<float>();
+  unsigned *wp = h->ws4.as<unsigned>();
+  dim3 g((unsigned)S, (unsigned)qtiles);
+#define FLAT_F16_GO(KP)                                                        \
+  (allow ? launch_flat_f16<KP, true, false>(h, g, 0, nq, 0, N, tps, allow, k,  \
+                                            wd, wp, nullptr, stream)           \
+         : launch_flat_f16<KP, false, false>(h, g, 0, nq, 0, N, tps, nullptr,  \
+                                             k, wd, wp, nullptr, stream))
+  if (k <= 4) FLAT_F16_GO(4);
+  else if (k <= 8) FLAT_F16_GO(8);
+  else FLAT_F16_GO(16);
+#undef FLAT_F16_GO
+  launch_merge_cand(stream, wd, wp, nq, (int)(S * k), k, nullptr,
+                    h->metric == M_IP, D, I, MERGE_WAVE);
+  HIP_CHECK(hipGetLastError());
+}
+
 // allow != nullptr: filtered (id-space bitmap; flat ids are positions)
 static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
                              float *D, int64_t *I, hipStream_t stream,
@@ -2441,6 +2586,22 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
     }
   }
   bool ip = h->metric == M_IP;
+  // fp16 store: the queries as fp16 rows and their norms,
+  // once per call; the database rows and norms are read as stored
+  const bool f16 = h->flat_f16;
+  if (f16) {
+    h->ws_bf16a.ensure((size_t)nq * h->flat_ldh * 2);
+    h->ws5.ensure((size_t)nq * 4);
+    flat_f16_rows(q, nq, h->d, h->flat_ldh, h->ws_bf16a.as<unsigned short>(),
+                  stream);
+    if (!ip)
+      flat_f16_norms(h->ws_bf16a.as<unsigned short>(), nq, h->flat_ldh,
+                     h->ws5.as<float>(), stream);
+    if (use_regsel(k)) {
+      flat_f16_fused(h, nq, k, D, I, stream, allow);
+      return;
+    }
+  }
   const int64_t CH = std::min<int64_t>(65536, std::max<int64_t>(
       4096, ((int64_t)h->ws_mb << 20) / (64 * 4)));
   int64_t nch = (h->ntotal + CH - 1) / CH;
@@ -2457,16 +2618,19 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
   float *qn = h->ws5.as<float>();
   float *wd = h->ws3.as<float>();
   unsigned *wp = h->ws4.as<unsigned>();
-  if (!ip) rownorms(q, nq, h->d, qn, stream);
+  if (!ip && !f16) rownorms(q, nq, h->d, qn, stream);
   for (int64_t ci = 0; ci < nch; ++ci) {
     int64_t b0 = ci * CH;
     int64_t bn_rows = std::min(CH, h->ntotal - b0);
     const float *base = h->flat.as<float>() + (size_t)b0 * h->d;
-    if (!ip) rownorms(base, bn_rows, h->d, bn, stream);
+    if (!ip && !f16) rownorms(base, bn_rows, h->d, bn, stream);
     for (int64_t s = 0; s < nq; s += qch) {
       int64_t c = std::min(qch, nq - s);
-      gemm_keys(h, q + s * h->d, c, base, bn_rows, h->d, bn, qn + s,
-                ip ? 0 : 2, sc, stream);
+      if (f16)
+        flat_f16_keys(h, s, c, b0, bn_rows, sc, stream);
+      else
+        gemm_keys(h, q + s * h->d, c, base, bn_rows, h->d, bn, qn + s,
+                  ip ? 0 : 2, sc, stream);
       // winners layout: (nq, nch, k) — row stride nch*k
       launch_topk_rows(stream, 256, sc, c, bn_rows, k, (unsigned)b0, nch * k,
                        wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
@@ -2948,7 +3112,10 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
   }
   int rtype;
   const float *flat_src = nullptr;
-  if (h->type == T_FLAT) { rtype = 0; flat_src = h->flat.as<float>(); }
+  if (h->type == T_FLAT) {
+    rtype = h->flat_f16 ? 9 : 0;
+    flat_src = h->flat.as<float>();
+  }
   else if (h->type == T_IVFFLAT) rtype = 0;
   else if (h->type == T_IVFPQ) rtype = h->nbits == 4 ? 6 : 2;
   else if (h->type == T_HNSW) rtype = 5;
@@ -3261,7 +3428,8 @@ extern "C" int dfann_save(dfann_index *h, const char *path) {
       dump_dev(f, h->hn_cntU, (size_t)h->hnsw_nslots * HNSW_MAXL * 4);
       dump_dev(f, h->hn_nbrU, (size_t)h->hnsw_nslots * HNSW_MAXL * h->m * 4);
     } else if (h->type == T_FLAT) {
-      dump_dev(f, h->flat, (size_t)h->ntotal * h->d * 4);
+      // fp16 store: the rows with their pad; norms are rebuilt on load
+      dump_dev(f, h->flat, (size_t)h->ntotal * h->code_bytes);
       if (v2)
         fwrite_chk(h->h_flat_live.data(), (size_t)((h->ntotal + 31) / 32) * 4,
                    f);
@@ -3395,7 +3563,14 @@ extern "C" int dfann_load(const char *path, dfann_index **out) {
         HIP_CHECK(hipDeviceSynchronize());
       }
     } else if (h->type == T_FLAT) {
-      load_dev(f, h->flat, (size_t)h->ntotal * h->d * 4);
+      load_dev(f, h->flat, (size_t)h->ntotal * h->code_bytes);
+      if (h->flat_f16 && h->metric == M_L2 && h->ntotal) {
+        // the kernel add uses: a loaded index is bitwise the saved one
+        h->flat_norm.ensure((size_t)h->ntotal * 4);
+        flat_f16_norms(h->flat.as<unsigned short>(), h->ntotal, h->flat_ldh,
+                       h->flat_norm.as<float>(), 0);
+        HIP_CHECK(hipDeviceSynchronize());
+      }
       if (v2) {
         h->h_flat_live.resize((size_t)((h->ntotal + 31) / 32));
         fread_chk(h->h_flat_live.data(), h->h_flat_live.size() * 4, f);

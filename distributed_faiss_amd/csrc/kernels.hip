@@ -701,6 +701,264 @@ __global__ __launch_bounds__(512) void k_gemm_bf16_256_topk(
 #undef GLDS_MAINLOOP
 
 // ---------------------------------------------------------------------------
+// flat fp16 store (spec "flat_store": "fp16"): brute-force
+// search over fp16 rows with the top-k fused into the GEMM.
+//
+// Rows (database and, per call, the queries) are ldh = round_up(d, 8) halves
+// with zero pad, so every row starts 16-byte aligned and a K block never
+// needs an element-wise tail: a 16-B group is either inside [0, ldh) or
+// staged as zeros. ||x||^2 of the ROUNDED values is kept in fp32 next to the
+// rows (k_flat_f16_norm, at add / load; the same kernel norms the queries).
+//
+// k_flat_f16: a block owns FH_TM = 128 query rows and a contiguous span of
+// FH_TN = 256-row database tiles (grid = (splits, query tiles)) and walks the
+// span. Per tile: K blocks of 64 halves go global -> LDS by 16-B
+// global_load_lds, double-buffered (2 x 48 KB), XOR swizzle on the source
+// group and on the fragment read (rule 21, as the bf16 kernels above); 8
+// waves as 2 (M) x 4 (N), wave tile 64 x 64 = acc[4][4] on
+// v_mfma_f32_16x16x32_f16. Then one of two epilogues on the same
+// accumulators and the same gemm_key():
+//   STORE  keys to C (N columns) — the k > 16 path, selected by k_topk_rows*
+//   fused  the operand buffer is reused as a 128 x 128 fp32 tile, filled in
+//          two passes (tj 0-1, then 2-3). Thread t owns row t >> 2 and the
+//          32-column chunk t & 3 of it and streams the chunk through a
+//          RegTopK<KP> that LIVES ACROSS THE TILES of the span: once warm, a
+//          losing key costs the one compare of push(). The start slot of
+//          the ds_read_b128 sequence is rotated so that the 16 lanes of a
+//          read group (4 rows x 4 chunks) hit 16 distinct 16-B slots of the
+//          256-B bank row. (key, position) is a strict total order, so
+//          neither the push order nor the split changes the result. After
+//          the span the four threads of a row merge by shuffle and one
+//          writes the row's first k pairs to cand[(row, split, k)];
+//          k_merge_cand* (null id table) finishes.
+// FILT gates each push on the id-space bit of the position (flat ids are
+// positions): the caller's allow bitmap, the tombstones, or their AND.
+// Registers: 64 accumulators + 2 KP state; no instantiation spills
+// (profiles/flat_f16).
+// ---------------------------------------------------------------------------
+
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+
+#define FH_TM 128
+#define FH_TN 256
+#define FH_K 64
+
+// (n x d) fp32 -> (n x ldh) fp16, round-to-nearest-even as k_refine_store_f16
+// and k_sq_encode; the pad is written too (fresh buffers are not cleared)
+extern "C" __global__ void k_flat_f16_store(const float *__restrict__ x,
+                                            long long n, int d, int ldh,
+                                            unsigned short *__restrict__ out) {
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long total = n * ldh;
+  for (; i < total; i += (long long)gridDim.x * blockDim.x) {
+    long long r = i / ldh;
+    int t = (int)(i % ldh);
+    out[i] = t < d ? __half_as_ushort(__float2half(x[r * d + t]))
+                   : (unsigned short)0;
+  }
+}
+
+// ||row||^2 of the stored halves in fp32, one wave per row (4 rows a block)
+extern "C" __global__ __launch_bounds__(256) void k_flat_f16_norm(
+    const unsigned short *__restrict__ rows, long long n, int ldh,
+    float *__restrict__ out) {
+  long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;
+  int lane = threadIdx.x & 63;
+  const unsigned short *rp = rows + row * ldh;
+  float acc = 0.f;
+  for (int t = lane; t < ldh; t += 64) {
+    float v = __half2float(__ushort_as_half(rp[t]));
+    acc += v * v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if (lane == 0) out[row] = acc;
+}
+
+// Stage K block k0 of ROWS operand rows (from row0 on, nrows in all) into
+// dst[ROWS][FH_K]: ROWS * 8 groups of 16 B = 8 waves x ROWS / 64 glds x 64
+// lanes, LDS image lane-linear, swizzle on the source group. A group outside
+// the operand (row >= nrows, or past ldh) is staged as zeros.
+template <int ROWS>
+__device__ __forceinline__ void fh_stage(unsigned short *dst,
+                                         const unsigned short *__restrict__ src,
+                                         long long row0, long long nrows,
+                                         int ldh, int k0, int w, int lane) {
+#pragma unroll
+  for (int i = 0; i < ROWS / 64; ++i) {
+    int gb = (w * (ROWS / 64) + i) * 64;  // the wave's first group
+    int g = gb + lane;
+    int r = g >> 3;
+    int c8s = ((g & 7) * 8) ^ ((r & 7) << 3);
+    if (row0 + r < nrows && k0 + c8s < ldh)
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int *)(
+              src + (size_t)(row0 + r) * ldh + k0 + c8s),
+          (__attribute__((address_space(3))) unsigned int *)(dst +
+                                                             (size_t)gb * 8),
+          16, 0, 0);
+    else
+      *reinterpret_cast<uint4 *>(dst + (size_t)g * 8) = uint4{0, 0, 0, 0};
+  }
+}
+
+// one staged K block: buf = [FH_TM query rows | FH_TN database rows][FH_K]
+__device__ __forceinline__ void fh_mfma(const unsigned short *buf,
+                                        f32x4 (&acc)[4][4], int wr, int wc,
+                                        int li, int ke) {
+  const unsigned short *sx = buf + FH_TM * FH_K;
+#pragma unroll
+  for (int kk = 0; kk < FH_K; kk += 32) {
+    f16x8 a[4];
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) {
+      int ra = wr + ti * 16 + li;
+      a[ti] = *reinterpret_cast<const f16x8 *>(
+          buf + ra * FH_K + ((kk + ke) ^ ((ra & 7) << 3)));
+    }
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) {
+      int rb = wc + tj * 16 + li;
+      f16x8 b = *reinterpret_cast<const f16x8 *>(
+          sx + rb * FH_K + ((kk + ke) ^ ((rb & 7) << 3)));
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+        acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+            a[ti], b, acc[ti][tj], 0, 0, 0);
+    }
+  }
+}
+
+// mode: gemm_key's (0 -ip, 2 (qn - 2ip) + bn). Positions are database rows
+// (N < 2^32). STORE: C is (M x N) keys. Fused: cand_* are (M, gridDim.x, k).
+template <int KP, bool FILT, bool STORE>
+__global__ __launch_bounds__(512) void k_flat_f16(
+    const unsigned short *__restrict__ Q, const unsigned short *__restrict__ X,
+    int M, long long N, int ldh, const float *__restrict__ qn,
+    const float *__restrict__ bn, int mode, int tiles_per_split,
+    const unsigned *__restrict__ allow, int k, float *__restrict__ cand_d,
+    unsigned *__restrict__ cand_p, float *__restrict__ C) {
+  __shared__ __attribute__((aligned(16)))
+  unsigned short fsm[2][FH_TM + FH_TN][FH_K];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int bi = blockIdx.y * FH_TM;
+  const int wr = (w >> 2) * 64, wc = (w & 3) * 64;
+  const int li = lane & 15, ke = (lane >> 4) * 8, rrow = (lane >> 4) * 4;
+  const long long ntiles = (N + FH_TN - 1) / FH_TN;
+  const long long t0 = (long long)blockIdx.x * tiles_per_split;
+  const long long t1 =
+      t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
+  // select ownership (fused): row srow of the block, chunk sch of a half
+  const int srow = tid >> 2, sch = tid & 3;
+  const int grow = bi + srow;
+  const int rot = ((tid >> 2) & 3) * 2 + ((tid & 3) >> 1);
+  RegTopK<KP> loc;
+  loc.init();
+
+  for (long long t = t0; t < t1; ++t) {
+    const long long bj = t * FH_TN;
+    f32x4 acc[4][4] = {};
+    fh_stage<FH_TM>(&fsm[0][0][0], Q, bi, M, ldh, 0, w, lane);
+    fh_stage<FH_TN>(&fsm[0][FH_TM][0], X, bj, N, ldh, 0, w, lane);
+    __syncthreads();
+    int cur = 0;
+    for (int k0 = FH_K; k0 < ldh; k0 += FH_K) {
+      // DMA of the next K block in flight during the MFMAs
+      fh_stage<FH_TM>(&fsm[cur ^ 1][0][0], Q, bi, M, ldh, k0, w, lane);
+      fh_stage<FH_TN>(&fsm[cur ^ 1][FH_TM][0], X, bj, N, ldh, k0, w, lane);
+      fh_mfma(&fsm[cur][0][0], acc, wr, wc, li, ke);
+      __syncthreads();  // drains the glds queue (vmcnt(0) inside)
+      cur ^= 1;
+    }
+    fh_mfma(&fsm[cur][0][0], acc, wr, wc, li, ke);
+    const float *bnt = bn ? bn + bj : bn;  // the tile's norms (L2)
+
+    if (STORE) {
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            int row = bi + wr + ti * 16 + rrow + rg;
+            long long col = bj + wc + tj * 16 + li;
+            if (row < M && col < N)
+              C[(size_t)row * N + col] =
+                  gemm_key(acc[ti][tj][rg], row, (int)(col - bj), qn, bnt, mode);
+          }
+      __syncthreads();  // operand buffers free for the next tile's stage
+      continue;
+    }
+
+    __syncthreads();  // every wave is done with the operand tiles
+    float *tile = reinterpret_cast<float *>(&fsm[0][0][0]);  // [128][128]
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      if (hf) __syncthreads();  // first half consumed
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int tjl = 0; tjl < 2; ++tjl)
+#pragma unroll
+          for (int rg = 0; rg < 4; ++rg) {
+            int lrow = wr + ti * 16 + rrow + rg;
+            int row = bi + lrow;
+            long long col = bj + wc + (hf * 2 + tjl) * 16 + li;
+            float key = DFANN_FLT_MAX;
+            if (row < M && col < N)
+              key = gemm_key(acc[ti][hf * 2 + tjl][rg], row, (int)(col - bj), qn,
+                             bnt, mode);
+            tile[lrow * 128 + (w & 3) * 32 + tjl * 16 + li] = key;
+          }
+      __syncthreads();
+      const float4 *rp =
+          reinterpret_cast<const float4 *>(tile + srow * 128 + sch * 32);
+#pragma unroll 2
+      for (int j = 0; j < 8; ++j) {
+        int s = (j + rot) & 7;
+        float4 v = rp[s];
+        // tile column -> database row (4 consecutive share a 16-col group)
+        int lc = s * 4;
+        long long col = bj + sch * 64 + (hf * 2 + (lc >> 4)) * 16 + (lc & 15);
+        if (grow < M) {
+          float kv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (col + e < N && (!FILT || pos_allowed(allow, col + e)))
+              loc.push(kv[e], (unsigned)(col + e));
+        }
+      }
+    }
+    __syncthreads();  // tile consumed before the next stage overwrites it
+  }
+  if (STORE) return;
+
+  // merge the row's four chunk lists (lanes t ^ 1, then t ^ 2)
+#pragma unroll
+  for (int x = 1; x <= 2; x <<= 1) {
+    float od[KP];
+    unsigned op[KP];
+#pragma unroll
+    for (int i = 0; i < KP; ++i) {
+      od[i] = __shfl_xor(loc.d[i], x, 64);
+      op[i] = __shfl_xor(loc.p[i], x, 64);
+    }
+#pragma unroll
+    for (int i = 0; i < KP; ++i) loc.push(od[i], op[i]);
+  }
+  if (sch == 0 && grow < M) {
+    size_t o = ((size_t)grow * gridDim.x + blockIdx.x) * k;
+#pragma unroll
+    for (int i = 0; i < KP; ++i)
+      if (i < k) {
+        cand_d[o + i] = loc.d[i];
+        cand_p[o + i] = loc.p[i];
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // row norms ||x_i||^2, one block per row
 // ---------------------------------------------------------------------------
 
@@ -3040,7 +3298,8 @@ extern "C" __global__ void k_minmax_decode(const unsigned *mn, const unsigned *m
 // reconstruction: decode result ids -> vectors. One block per (q, j).
 // type: 0 flat/ivfflat raw (flat_src != null uses flat arena directly by id,
 // else CSR codes row), 2 pq, 3 sq8, 4 sqfp16, 5 hnsw sq8, 6 pq nbits=4,
-// 7 sq4, 8 sq6 (packed bit streams)
+// 7 sq4, 8 sq6 (packed bit streams), 9 flat fp16 rows
+// (flat_src holds them, `stride` bytes apart)
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
@@ -3058,6 +3317,13 @@ extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
   float *out = R + e * d;
   if (id < 0) {
     for (int t = threadIdx.x; t < d; t += blockDim.x) out[t] = 0.f;
+    return;
+  }
+  if (type == 9) {  // flat fp16: the stored halves widened, rows by id
+    const unsigned short *hp = reinterpret_cast<const unsigned short *>(
+        reinterpret_cast<const uint8_t *>(flat_src) + (size_t)id * stride);
+    for (int t = threadIdx.x; t < d; t += blockDim.x)
+      out[t] = __half2float(__ushort_as_half(hp[t]));
     return;
   }
   if (flat_src) {

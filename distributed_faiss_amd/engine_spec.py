@@ -7,7 +7,7 @@
 # oracle. Engine spec keys:
 #   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq"
 #   dim, metric (0=IP, 1=L2), nlist, m, nbits (ivfpq: 4 | 8; DESIGN.md
-#   §6d), sq_type ("fp16"|"8bit"|"6bit"|"4bit"), nprobe, seed
+#   §6d), flat_store ("fp32"|"fp16", flat only), sq_type ("fp16"|"8bit"|"6bit"|"4bit"), nprobe, seed
 #   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
 #   (faiss IndexRefineFlat / IndexRefine)
 #   opq (1), opq_dim, opq_niter: learned orthonormal pre-transform in front
@@ -58,6 +58,8 @@ def _builder_spec(cfg: IndexCfg) -> dict:
     if t == "flat":
         # reference index.py:94 — always IP, metric ignored (quirk 3)
         spec.update(type="flat", metric=METRIC_INNER_PRODUCT)
+        if "flat_store" in cfg.extra:
+            spec["flat_store"] = str(cfg.extra["flat_store"])
         return spec
     if t == "ivf_simple":
         # reference index.py:36-40
@@ -120,6 +122,10 @@ REFINE_KEYS = ("refine", "k_factor")
 # OPQ keys of cfg.extra (builder knnlm; "opq_niter" also with an OPQ factory
 # string). Result-changing like REFINE_KEYS, not perf knobs.
 OPQ_KEYS = ("opq", "opq_dim", "opq_niter")
+# Row format of the flat store (builder flat; the factory string "SQfp16" is
+# faiss IndexScalarQuantizer(d, QT_fp16)). Result-changing too: fp16 rows
+# round the data and the queries.
+FLAT_KEYS = ("flat_store",)
 
 
 def _apply_opq(cfg: IndexCfg, spec: dict) -> dict:
@@ -157,10 +163,13 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if s == "Flat":
         spec.update(type="flat")
         return spec
+    if s == "SQfp16":
+        spec.update(type="flat", flat_store="fp16")
+        return spec
     mm = _FACTORY_RE.match(s)
     if not mm:
         raise NotImplementedError(
-            f"factory string {s!r} not supported; supported: Flat, IVFn,Flat, "
+            f"factory string {s!r} not supported; supported: Flat, SQfp16, IVFn,Flat, "
             "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQ6, IVFn,SQ4, "
             "IVFn,SQfp16, "
             "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16), and "

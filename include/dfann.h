@@ -116,6 +116,14 @@ typedef void *dfann_stream;             /* hipStream_t */
  * "slab_mb" (ivf types; default 64, clamped to 1..4096): size of the slabs
  * the inverted-list codes and the pending appends live in; the list merge
  * and dfann_remove_ids work through them one slab at a time.
+ * "flat" rows: "flat_store": "fp32" (default; dim floats per row) | "fp16"
+ * (faiss IndexScalarQuantizer(d, QT_fp16)): rows of
+ * round_up(dim, 8) halves, __float2half of the input (a value above 65504
+ * becomes inf), zero pad; dfann_code_stride is that row in bytes. Searches
+ * round the queries to fp16 as well and return the distance between the
+ * rounded operands, accumulated in fp32; dfann_search_reconstruct returns
+ * the stored halves widened. Another value, or the key on another index
+ * type, is an error naming the key.
  * "ivfpq" codes: "nbits" (default 8) bits per sub-quantizer, 1 << nbits
  * codewords each; any other value is an error. At 8 a row is m bytes; at
  * 4 it is (m + 1) / 2 bytes, byte b = code[2b] |
