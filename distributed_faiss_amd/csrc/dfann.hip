@@ -372,7 +372,11 @@ struct dfann_index {
   // call; range_ws = [wave counts | offsets | per-query totals | error word]
   int64_t range_max = 1LL << 27;  // spec "range_max_results"
   DevBuf range_D, range_I, range_ws;
-  DevBuf filt_ws;    // filtered search: allow-bitmap in CSR-position space
+  // large k: spec "k_max"; every candidate of a query chunk
+  // as a ragged (lims, D, I) of its own, at most range_max entries
+  int k_max = 512;
+  DevBuf lk_D, lk_I, lk_lims;
+  DevBuf filt_ws;   // filtered search: allow-bitmap in CSR-position space
                      // (rebuilt by k_filter_id2pos on every filtered call)
   // removal. ivf: keep words, their popcounts and the int64
   // prefix of one compaction. flat: the tombstones, a live bitmap over ids
@@ -428,6 +432,20 @@ struct dfann_index {
 // ---------------------------------------------------------------------------
 
 static bool use_regsel(int k) { return k <= 16; }
+// k cap of the Sel-buffer kernels (SEL_CAP / 2); above it, up to the index's
+// k_max <= SEG_KMAX, k_select_seg
+static const int K_SEL_MAX = 512;
+
+// one block per query over any of the four sources of k_select_seg; the
+// vector loads need the key (and id) arrays 16-byte aligned
+template <class Src>
+static void launch_select_seg(hipStream_t stream, const Src &src, int64_t nq,
+                              int k, const void *keys, const void *ids) {
+  if (nq == 0) return;
+  const int vec = (((uintptr_t)keys | (uintptr_t)ids) & 15) == 0;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select_seg<Src>), dim3((unsigned)nq),
+                     dim3(SEG_BS), 0, stream, src, (long long)nq, k, vec);
+}
 
 // PQ codewords per sub-quantizer: 256 (nbits=8) or 16 (nbits=4)
 static int pq_ksub(const dfann_index *h) { return 1 << h->nbits; }
@@ -1203,6 +1221,22 @@ static dfann_index *create_from_spec(const std::string &js) {
   } else if (json_float(js, "k_factor", 1.0) < 1.0) {
     delete h;
     throw std::runtime_error("k_factor must be >= 1");
+  }
+  // largest k served: above 512 the large-k path, which
+  // synchronizes the stream, takes 512 < k <= k_max
+  h->k_max = (int)json_int(js, "k_max", K_SEL_MAX);
+  {
+    std::string bad;
+    if (h->k_max < K_SEL_MAX || h->k_max > SEG_KMAX)
+      bad = "k_max=" + std::to_string(h->k_max) + " must be in " +
+            std::to_string(K_SEL_MAX) + ".." + std::to_string(SEG_KMAX);
+    else if (h->k_max > K_SEL_MAX && h->type == T_HNSW)
+      bad = "k_max > 512 unsupported for hnswsq (the search list is capped "
+            "at 512)";
+    else if (h->k_max > K_SEL_MAX && h->refine)
+      bad = "k_max > 512 unsupported with refine (the base stage returns at "
+            "most 512 candidates)";
+    if (!bad.empty()) { delete h; throw std::runtime_error(bad); }
   }
   return h;
 }
@@ -2358,11 +2392,20 @@ static void scan_account(dfann_index *h, int64_t nq, int nprobe,
   h->scan_bytes += rows * h->stride;
 }
 
+static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
+                        const int32_t *probes, const float *keys, int k,
+                        float *D, int64_t *I, hipStream_t stream,
+                        const uint32_t *allow);
+
 static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                            int nprobe, const int32_t *probes,
                            const float *keys, int k, float *D, int64_t *I,
                            hipStream_t stream,
                            const uint32_t *allow = nullptr) {
+  if (k > K_SEL_MAX) {
+    large_k_ivf(h, nq, q, nprobe, probes, keys, k, D, I, stream, allow);
+    return;
+  }
   const bool ip = h->metric == M_IP;
   const ScanJob j = scan_prepare(h, nq, q, nprobe, k, stream, allow, false);
   const int fan = j.p.fan;
@@ -2405,10 +2448,14 @@ static void range_check(const dfann_index *h, const uint32_t *allow,
         " ids but the index holds " + std::to_string(h->ntotal));
 }
 
+// The (D, I) go to dst_D / dst_I (grown to the total). over != nullptr: a
+// total above range_max sets *over and returns after the count pass
+// instead of throwing.
 static void range_scan(dfann_index *h, int64_t nq, const float *q, int nprobe,
                        const int32_t *probes, const float *keys, float radius,
                        const uint32_t *allow, int64_t *lims, int64_t *total_out,
-                       hipStream_t stream) {
+                       hipStream_t stream, DevBuf &dst_D, DevBuf &dst_I,
+                       bool *over = nullptr) {
   const ScanJob j = scan_prepare(h, nq, q, nprobe, 1, stream, allow, true);
   const int W = (int)j.p.scan_bs / 64;
   // workspace: offsets and counts for 8 waves per (query, probe) whatever
@@ -2430,8 +2477,8 @@ static void range_scan(dfann_index *h, int64_t nq, const float *q, int nprobe,
                   a.range_off = off + q0 * nprobe * W;
                   a.range_lims = lims + q0;
                   a.cr_ids = h->cr_ids.as<int64_t>();
-                  a.range_D = h->range_D.as<float>();
-                  a.range_I = h->range_I.as<int64_t>();
+                  a.range_D = dst_D.as<float>();
+                  a.range_I = dst_I.as<int64_t>();
                   a.range_err = err;
                 });
     scan_account(h, nq, nprobe, probes);
@@ -2446,13 +2493,17 @@ static void range_scan(dfann_index *h, int64_t nq, const float *q, int nprobe,
   HIP_CHECK(hipMemcpyAsync(&total, lims + nq, 8, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   *total_out = total;
+  if (total > h->range_max && over) {  // the caller splits its batch
+    *over = true;
+    return;
+  }
   if (total > h->range_max)
     throw std::runtime_error(
         "range search: " + std::to_string(total) +
         " results exceed range_max_results = " + std::to_string(h->range_max));
   if (total == 0) return;
-  h->range_D.ensure((size_t)total * 4);
-  h->range_I.ensure((size_t)total * 8);
+  dst_D.ensure((size_t)total * 4);
+  dst_I.ensure((size_t)total * 8);
   pass(1);
   // a fill pass that met another hit count than the count pass stored
   // nothing outside its segment and raised the error word
@@ -2493,10 +2544,57 @@ static void range_impl(dfann_index *h, int64_t nq, const float *q_dev,
       throw std::runtime_error("range search: nprobe must be in 1..512");
     }
     range_scan(h, nq, qi, nprobe, probes, keys, radius, allow, lims, total_out,
-               stream);
+               stream, h->range_D, h->range_I);
   }
   *D_out = h->range_D.as<float>();
   *I_out = h->range_I.as<int64_t>();
+}
+
+// ---------------------------------------------------------------------------
+// large k on the IVF indexes: every candidate of the probed
+// lists through the range fill at the radius that admits all below the
+// sentinel, then k_select_seg over each query's segment. The ragged buffer
+// is the index's own (lk_D / lk_I: range_D / range_I stay the caller's
+// until the next range call) and holds at most range_max entries: the
+// queries go in chunks, a chunk whose count pass reports more is halved.
+// Synchronizes the stream (the count pass' total), twice per chunk.
+// ---------------------------------------------------------------------------
+static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
+                        const int32_t *probes, const float *keys, int k,
+                        float *D, int64_t *I, hipStream_t stream,
+                        const uint32_t *allow) {
+  const bool ip = h->metric == M_IP;
+  const float radius = ip ? -DFANN_FLT_MAX : DFANN_FLT_MAX;
+  int64_t step = nq;
+  for (int64_t q0 = 0; q0 < nq;) {
+    const int64_t c = std::min(step, nq - q0);
+    h->lk_lims.ensure((size_t)(c + 1) * 8);
+    int64_t *lims = h->lk_lims.as<int64_t>();
+    int64_t total = 0;
+    bool over = false;
+    range_scan(h, c, q + q0 * h->d, nprobe, probes + q0 * nprobe,
+               keys + q0 * nprobe, radius, allow, lims, &total, stream,
+               h->lk_D, h->lk_I, &over);
+    if (over) {
+      if (c == 1)
+        throw std::runtime_error(
+            "k_max: the probed lists of one query hold " +
+            std::to_string(total) +
+            " candidates, above range_max_results = " +
+            std::to_string(h->range_max));
+      step = (c + 1) / 2;
+      continue;
+    }
+    TimingEv em;
+    if (h->timing) em = h->ev_begin(stream);
+    SegRagged src = {reinterpret_cast<const long long *>(lims),
+                     h->lk_D.as<float>(), h->lk_I.as<int64_t>(), ip ? 1 : 0,
+                     D + q0 * k, I + q0 * k};
+    launch_select_seg(stream, src, c, k, src.D, src.I);
+    if (h->timing) h->ev_end(em, stream, h->ev_merge);
+    HIP_CHECK(hipGetLastError());
+    q0 += c;
+  }
 }
 
 // flat fp16: one k_flat_f16 launch over query rows
@@ -2632,16 +2730,27 @@ static void flat_search_impl(dfann_index *h, int64_t nq, const float *q, int k,
         gemm_keys(h, q + s * h->d, c, base, bn_rows, h->d, bn, qn + s,
                   ip ? 0 : 2, sc, stream);
       // winners layout: (nq, nch, k) — row stride nch*k
-      launch_topk_rows(stream, 256, sc, c, bn_rows, k, (unsigned)b0, nch * k,
-                       wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
-                       allow);
+      if (k > K_SEL_MAX) {
+        SegKeys src = {sc, bn_rows, bn_rows, (unsigned)b0, allow, nch * k,
+                       wd + (s * nch + ci) * k, wp + (s * nch + ci) * k};
+        launch_select_seg(stream, src, c, k, sc, nullptr);
+      } else {
+        launch_topk_rows(stream, 256, sc, c, bn_rows, k, (unsigned)b0, nch * k,
+                         wd + (s * nch + ci) * k, wp + (s * nch + ci) * k,
+                         allow);
+      }
     }
   }
   // merge chunk winners (flat ids are positions: no id table; block-per-
   // query kernels only: MERGE_RK excludes just the wave path, k > 16 still
   // goes to the LDS kernel)
-  launch_merge_cand(stream, wd, wp, nq, (int)(nch * k), k, nullptr, ip, D, I,
-                    MERGE_RK);
+  if (k > K_SEL_MAX) {
+    SegCand src = {wd, wp, nch * k, ip ? 1 : 0, D, I};
+    launch_select_seg(stream, src, nq, k, wd, wp);
+  } else {
+    launch_merge_cand(stream, wd, wp, nq, (int)(nch * k), k, nullptr, ip, D, I,
+                      MERGE_RK);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2661,9 +2770,10 @@ static void check_filter(dfann_index *h, const uint32_t *allow,
 // bounds its nprobe in range_impl). The probe VALUES are not checked: that
 // would need a host sync, and the scans treat a probe outside [0, nlist)
 // as an empty slot.
-static void check_preassigned(int k, int nprobe) {
-  if (k > 512)
-    throw std::runtime_error("search_preassigned: k > 512 unsupported (k = " +
+static void check_preassigned(const dfann_index *h, int k, int nprobe) {
+  if (k > h->k_max)
+    throw std::runtime_error("search_preassigned: k > " +
+                             std::to_string(h->k_max) + " unsupported (k = " +
                              std::to_string(k) + ")");
   if (k < 1)
     throw std::runtime_error("search_preassigned: k < 1 (k = " +
@@ -2678,7 +2788,9 @@ static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
                         float *D, int64_t *I, hipStream_t stream,
                         const uint32_t *allow = nullptr) {
   if (!h->trained) throw std::runtime_error("search on untrained index");
-  if (k > 512) throw std::runtime_error("k > 512 unsupported");
+  if (k > h->k_max)
+    throw std::runtime_error("k > " + std::to_string(h->k_max) +
+                             " unsupported");
   if (nq == 0) return;
   if (h->type == T_FLAT) {
     flat_search_impl(h, nq, q, k, D, I, stream, allow);
@@ -2963,7 +3075,7 @@ extern "C" int dfann_search_preassigned(dfann_index *h, int64_t nq,
   API_BEGIN
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
-  check_preassigned(k, nprobe);
+  check_preassigned(h, k, nprobe);
   if (nq == 0) return 0;
   if (!probes_dev || !keys_dev)
     throw std::runtime_error("search_preassigned: null probes / keys");
@@ -3009,7 +3121,7 @@ extern "C" int dfann_search_preassigned_filtered(
   if (!h->trained || h->type == T_FLAT)
     throw std::runtime_error("search_preassigned needs a trained IVF index");
   check_filter(h, allow_bits_dev, nbits);
-  check_preassigned(k, nprobe);
+  check_preassigned(h, k, nprobe);
   if (nq == 0) return 0;
   if (!probes_dev || !keys_dev)
     throw std::runtime_error("search_preassigned: null probes / keys");
@@ -3333,7 +3445,13 @@ extern "C" int dfann_merge_topk(int64_t nq, int S, int k, const float *D_dev,
                                 dfann_stream stream) {
   API_BEGIN
   (void)I_dev;  // slots map to metadata host-side (ref client.py:297-298)
-  if (k > 512) throw std::runtime_error("k > 512 unsupported");
+  if (k > SEG_KMAX) throw std::runtime_error("k > 2048 unsupported");
+  if (k > K_SEL_MAX) {
+    SegShards src = {D_dev, (long long)nq, S, maximize, Dout_dev, Iout_dev};
+    launch_select_seg((hipStream_t)stream, src, nq, k, D_dev, nullptr);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   const MergeLaunch m = merge_launch(nq, k, (int64_t)S * k);
   auto kern = m.path == MERGE_WAVE ? k_merge_shards_w
               : m.path == MERGE_RK ? k_merge_shards_rk

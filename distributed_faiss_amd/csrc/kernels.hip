@@ -2804,6 +2804,452 @@ extern "C" __global__ __launch_bounds__(256) void k_merge_shards_w(
 }
 
 // ---------------------------------------------------------------------------
+// k_select_seg: the k best of ONE LONG candidate segment per query, for
+// 512 < k <= SEG_KMAX. One block per query.
+//
+// Order = sel_less on (minimize-key, id as u32). For the select a candidate
+// is one 64-bit composite: the key as an order-preserving u32 (zero
+// canonicalised, then sign flip / full flip) over the id. The k-th smallest
+// composite is found by an MSB-first radix select: pass 0 sweeps the
+// segment for the admitted count and the min / max composite (the bits they
+// share are known and never histogrammed), then one sweep per SEG_RADIX-bit
+// digit builds an LDS histogram of the candidates that still match the
+// known prefix, and a block scan picks the bucket that holds rank k. It
+// stops when that bucket is needed whole — on ordinary data inside the key
+// half. A last sweep appends everything below the threshold, plus as many
+// equal to it as are still needed (exact duplicates), to an LDS buffer as
+// RAW (key, id), so that -0.0 / +0.0 leave as they came; a bitonic sort
+// under sel_less orders it.
+//
+// A segment of at most SEG_RES_CAP candidates is copied to LDS by pass 0
+// and every later sweep runs there; a longer one is swept from global
+// memory with two 16-byte key loads in flight per lane. A segment with at
+// most k admitted candidates skips the select.
+//
+// Deterministic: the selected SET is a function of the input and the sort
+// fixes the order, so the LDS atomics (histogram, append) cannot show.
+// Never admitted: what sel_less does not place before (FLT_MAX, PAD_POS).
+// ---------------------------------------------------------------------------
+#define SEG_KMAX 2048     // k cap; entries of the collect / sort buffer
+#define SEG_RES_CAP 4096  // candidates held in LDS (32 KB; 49 KB a block,
+                          // three blocks a CU)
+#define SEG_BS 512
+#define SEG_RADIX 8       // digit width; 256-bin histogram
+
+__device__ __forceinline__ float seg_nan() { return __uint_as_float(0x7FC00000u); }
+
+__device__ __forceinline__ bool seg_admit(float key, unsigned id) {
+  return sel_less(key, id, DFANN_FLT_MAX, PAD_POS);
+}
+
+__device__ __forceinline__ unsigned long long seg_comp(float key, unsigned id) {
+  unsigned b = __float_as_uint(key == 0.f ? 0.f : key);
+  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ((unsigned long long)b << 32) | id;
+}
+
+__device__ __forceinline__ unsigned long long seg_shfl_xor64(
+    unsigned long long v, int o) {
+  unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64);
+  unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// final (D, I) in faiss conventions — the output edge of k_merge_cand
+__device__ __forceinline__ void seg_store_final(float *__restrict__ D,
+                                                int64_t *__restrict__ I,
+                                                long long o, int is_ip,
+                                                bool valid, float key,
+                                                unsigned id) {
+  if (valid) {
+    D[o] = is_ip ? -key : key;
+    I[o] = (long long)id;
+  } else {
+    D[o] = is_ip ? -DFANN_FLT_MAX : DFANN_FLT_MAX;
+    I[o] = -1;
+  }
+}
+
+// Source policies. A query's candidates are runs() runs of consecutive
+// elements [beg, end) of the key array, element `a` of a run having the
+// implicit id id0 + (a - beg). load1 / load4 (elements 4g .. 4g+3, the
+// arrays 16-byte aligned) return the minimize-key and the id; what is no
+// candidate gets a NaN key. store writes output column j.
+
+// 1: ragged (lims, D, I64) — the range fill output, D un-negated
+struct SegRagged {
+  const long long *lims;
+  const float *D;
+  const int64_t *I;
+  int is_ip;
+  float *oD;
+  int64_t *oI;
+  __device__ int runs() const { return 1; }
+  __device__ void run(long long q, int, int, long long &beg, long long &end,
+                      unsigned &id0) const {
+    beg = lims[q]; end = lims[q + 1]; id0 = 0;
+  }
+  __device__ void load1(long long a, unsigned, float &key, unsigned &id) const {
+    float v = D[a];
+    key = is_ip ? -v : v;
+    id = (unsigned)I[a];
+  }
+  __device__ void load4(long long g, unsigned, float (&key)[4],
+                        unsigned (&id)[4]) const {
+    float4 v = reinterpret_cast<const float4 *>(D)[g];
+    const ulonglong2 *ip = reinterpret_cast<const ulonglong2 *>(I) + 2 * g;
+    ulonglong2 i0 = ip[0], i1 = ip[1];
+    key[0] = is_ip ? -v.x : v.x; key[1] = is_ip ? -v.y : v.y;
+    key[2] = is_ip ? -v.z : v.z; key[3] = is_ip ? -v.w : v.w;
+    id[0] = (unsigned)i0.x; id[1] = (unsigned)i0.y;
+    id[2] = (unsigned)i1.x; id[3] = (unsigned)i1.y;
+  }
+  __device__ void store(long long q, int j, int k, bool valid, float key,
+                        unsigned id) const {
+    seg_store_final(oD, oI, q * k + j, is_ip, valid, key, id);
+  }
+};
+
+// 2: dense key rows, id = base + col, optional allow bitmap over ids; the
+// output is a (key, u32 pos) candidate row as k_topk_rows writes it
+struct SegKeys {
+  const float *keys;
+  long long cols, ldk;
+  unsigned base;
+  const unsigned *allow;
+  long long ldo;
+  float *od;
+  unsigned *op;
+  __device__ int runs() const { return 1; }
+  __device__ void run(long long q, int, int, long long &beg, long long &end,
+                      unsigned &id0) const {
+    beg = q * ldk; end = beg + cols; id0 = base;
+  }
+  __device__ void load1(long long a, unsigned idimp, float &key,
+                        unsigned &id) const {
+    key = keys[a];
+    id = idimp;
+    if (allow && !pos_allowed(allow, id)) key = seg_nan();
+  }
+  __device__ void load4(long long g, unsigned idimp, float (&key)[4],
+                        unsigned (&id)[4]) const {
+    float4 v = reinterpret_cast<const float4 *>(keys)[g];
+    key[0] = v.x; key[1] = v.y; key[2] = v.z; key[3] = v.w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      id[e] = idimp + e;
+      if (allow && !pos_allowed(allow, id[e])) key[e] = seg_nan();
+    }
+  }
+  __device__ void store(long long q, int j, int, bool valid, float key,
+                        unsigned id) const {
+    od[q * ldo + j] = valid ? key : DFANN_FLT_MAX;
+    op[q * ldo + j] = valid ? id : PAD_POS;
+  }
+};
+
+// 3: dense (key, u32 pos) candidate rows, PAD_POS skipped, pos is the id
+struct SegCand {
+  const float *cd;
+  const unsigned *cp;
+  long long C;
+  int is_ip;
+  float *oD;
+  int64_t *oI;
+  __device__ int runs() const { return 1; }
+  __device__ void run(long long q, int, int, long long &beg, long long &end,
+                      unsigned &id0) const {
+    beg = q * C; end = beg + C; id0 = 0;
+  }
+  __device__ void load1(long long a, unsigned, float &key, unsigned &id) const {
+    key = cd[a];
+    id = cp[a];
+    if (id == PAD_POS) key = seg_nan();
+  }
+  __device__ void load4(long long g, unsigned, float (&key)[4],
+                        unsigned (&id)[4]) const {
+    float4 v = reinterpret_cast<const float4 *>(cd)[g];
+    uint4 p = reinterpret_cast<const uint4 *>(cp)[g];
+    key[0] = v.x; key[1] = v.y; key[2] = v.z; key[3] = v.w;
+    id[0] = p.x; id[1] = p.y; id[2] = p.z; id[3] = p.w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (id[e] == PAD_POS) key[e] = seg_nan();
+  }
+  __device__ void store(long long q, int j, int k, bool valid, float key,
+                        unsigned id) const {
+    seg_store_final(oD, oI, q * k + j, is_ip, valid, key, id);
+  }
+};
+
+// 4: the (S, nq, k) shard layout of k_merge_shards — every slot a candidate
+// (pads included), id = dense slot s*k + j; the output keeps the maximize
+// negation (quirk 2) and carries global slots, an unfilled column what
+// k_merge_shards makes of its (FLT_MAX, PAD_POS) pad
+struct SegShards {
+  const float *Dall;
+  long long nq;
+  int S;
+  int maximize;
+  float *Dout;
+  int64_t *Iout;
+  __device__ int runs() const { return S; }
+  __device__ void run(long long q, int r, int k, long long &beg, long long &end,
+                      unsigned &id0) const {
+    beg = ((long long)r * nq + q) * k; end = beg + k; id0 = (unsigned)(r * k);
+  }
+  __device__ void load1(long long a, unsigned idimp, float &key,
+                        unsigned &id) const {
+    float v = Dall[a];
+    key = maximize ? -v : v;
+    id = idimp;
+  }
+  __device__ void load4(long long g, unsigned idimp, float (&key)[4],
+                        unsigned (&id)[4]) const {
+    float4 v = reinterpret_cast<const float4 *>(Dall)[g];
+    key[0] = maximize ? -v.x : v.x; key[1] = maximize ? -v.y : v.y;
+    key[2] = maximize ? -v.z : v.z; key[3] = maximize ? -v.w : v.w;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) id[e] = idimp + e;
+  }
+  __device__ void store(long long q, int j, int k, bool valid, float key,
+                        unsigned id) const {
+    if (!valid) { key = DFANN_FLT_MAX; id = PAD_POS; }
+    unsigned sh = id / (unsigned)k, jj = id % (unsigned)k;
+    Dout[q * k + j] = key;
+    Iout[q * k + j] = ((long long)sh * nq + q) * k + jj;
+  }
+};
+
+// elements 4g .. 4g+3 of a run: one vector load when the group lies inside
+// the run (vec: the arrays are 16-byte aligned), element loads at its ragged
+// ends — nothing outside [beg, end) is ever read
+template <class Src>
+__device__ __forceinline__ void seg_load4(const Src &s, long long g,
+                                          long long beg, long long end,
+                                          unsigned id0, int vec,
+                                          float (&key)[4], unsigned (&id)[4]) {
+  const long long a0 = g * 4;
+  const unsigned idimp = id0 + (unsigned)(a0 - beg);
+  if (vec && a0 >= beg && a0 + 4 <= end) {
+    s.load4(g, idimp, key, id);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    key[e] = seg_nan();
+    id[e] = PAD_POS;
+    if (a0 + e >= beg && a0 + e < end) s.load1(a0 + e, idimp + e, key[e], id[e]);
+  }
+}
+
+template <class F>
+__device__ __forceinline__ void seg_visit4(long long g, long long beg,
+                                           long long end, unsigned ord0,
+                                           const float (&key)[4],
+                                           const unsigned (&id)[4],
+                                           float *resd, unsigned *resp,
+                                           bool keep, F &f) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long a = g * 4 + e;
+    if (a < beg || a >= end) continue;
+    if (keep) {
+      resd[ord0 + (unsigned)(a - beg)] = key[e];
+      resp[ord0 + (unsigned)(a - beg)] = id[e];
+    }
+    if (seg_admit(key[e], id[e])) f(key[e], id[e]);
+  }
+}
+
+// one sweep of query q's candidates from global memory, f(key, id) on each
+// admitted one; keep: also copy every candidate to resd / resp (dense order)
+template <class Src, class F>
+__device__ __forceinline__ void seg_sweep(const Src &s, long long q, int k,
+                                          int vec, float *resd, unsigned *resp,
+                                          bool keep, F &f) {
+  unsigned ord0 = 0;
+  for (int r = 0; r < s.runs(); ++r) {
+    long long beg, end;
+    unsigned id0;
+    s.run(q, r, k, beg, end, id0);
+    const long long g1 = (end + 3) >> 2;
+    for (long long g = (beg >> 2) + threadIdx.x; g < g1; g += 2 * SEG_BS) {
+      float ka[4], kb[4];
+      unsigned ia[4], ib[4];
+      const long long gb = g + SEG_BS;
+      const bool hb = gb < g1;
+      seg_load4(s, g, beg, end, id0, vec, ka, ia);
+      if (hb) seg_load4(s, gb, beg, end, id0, vec, kb, ib);
+      seg_visit4(g, beg, end, ord0, ka, ia, resd, resp, keep, f);
+      if (hb) seg_visit4(gb, beg, end, ord0, kb, ib, resd, resp, keep, f);
+    }
+    ord0 += (unsigned)(end - beg);
+  }
+}
+
+// a query's candidates number less than 2^32 (the host bounds a segment)
+template <class Src>
+__global__ __launch_bounds__(SEG_BS) void k_select_seg(Src src, long long nq,
+                                                       int k, int vec) {
+  __shared__ float resd[SEG_RES_CAP];
+  __shared__ unsigned resp[SEG_RES_CAP];
+  __shared__ float outd[SEG_KMAX];
+  __shared__ unsigned outp[SEG_KMAX];
+  __shared__ unsigned hist[1 << SEG_RADIX];
+  __shared__ unsigned long long wmin[SEG_BS / 64], wmax[SEG_BS / 64];
+  __shared__ unsigned wcnt[SEG_BS / 64];
+  // taken, taken among the threshold's equals, bucket, its count, the count
+  // of the buckets below it
+  __shared__ unsigned ctrl[5];
+  const long long q = blockIdx.x;
+  if (q >= nq) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+
+  long long n = 0;
+  for (int r = 0; r < src.runs(); ++r) {
+    long long beg, end;
+    unsigned id0;
+    src.run(q, r, k, beg, end, id0);
+    n += end - beg;
+  }
+  const bool resident = n <= SEG_RES_CAP;
+  auto each = [&](auto f) {
+    if (resident) {
+      for (int i = tid; i < (int)n; i += SEG_BS) {
+        float key = resd[i];
+        unsigned id = resp[i];
+        if (seg_admit(key, id)) f(key, id);
+      }
+    } else {
+      seg_sweep(src, q, k, vec, resd, resp, false, f);
+    }
+  };
+
+  // pass 0: admitted count, min / max composite; LDS copy when resident
+  unsigned cnt = 0;
+  unsigned long long mn = ~0ull, mx = 0ull;
+  {
+    auto f0 = [&](float key, unsigned id) {
+      unsigned long long c = seg_comp(key, id);
+      ++cnt;
+      mn = c < mn ? c : mn;
+      mx = c > mx ? c : mx;
+    };
+    seg_sweep(src, q, k, vec, resd, resp, resident, f0);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
+    unsigned long long a = seg_shfl_xor64(mn, o), b = seg_shfl_xor64(mx, o);
+    mn = a < mn ? a : mn;
+    mx = b > mx ? b : mx;
+  }
+  if (lane == 0) { wcnt[w] = cnt; wmin[w] = mn; wmax[w] = mx; }
+  if (tid == 0) { ctrl[0] = 0; ctrl[1] = 0; }
+  __syncthreads();
+  unsigned nadm = 0;
+  mn = ~0ull; mx = 0ull;
+  for (int i = 0; i < SEG_BS / 64; ++i) {
+    nadm += wcnt[i];
+    mn = wmin[i] < mn ? wmin[i] : mn;
+    mx = wmax[i] > mx ? wmax[i] : mx;
+  }
+
+  // threshold: take (c & kmask) < kval, and `need` of those == kval.
+  // kmask = 0 takes every admitted candidate.
+  unsigned long long kmask = 0ull, kval = 0ull;
+  unsigned need = nadm;
+  if (nadm > (unsigned)k) {
+    need = (unsigned)k;
+    int shift = mn == mx ? 0 : 64 - __clzll((long long)(mn ^ mx));
+    kmask = shift >= 64 ? 0ull : ~0ull << shift;  // bits min and max share
+    kval = mn & kmask;
+    while (shift > 0) {
+      const int nb = shift < SEG_RADIX ? shift : SEG_RADIX;
+      shift -= nb;
+      const unsigned dm = (1u << nb) - 1u;
+      if (tid < (1 << SEG_RADIX)) hist[tid] = 0;
+      __syncthreads();
+      each([&](float key, unsigned id) {
+        unsigned long long c = seg_comp(key, id);
+        if ((c & kmask) == kval)
+          atomicAdd(&hist[(unsigned)(c >> shift) & dm], 1u);
+      });
+      __syncthreads();
+      // the bucket b with excl(b) < need <= incl(b): waves 0..3 scan
+      unsigned c = 0, incl = 0;
+      if (tid < (1 << SEG_RADIX)) {
+        c = hist[tid];
+        incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          unsigned t = (unsigned)__shfl_up((int)incl, o, 64);
+          if (lane >= o) incl += t;
+        }
+        if (lane == 63) wcnt[w] = incl;
+      }
+      __syncthreads();
+      if (tid < (1 << SEG_RADIX)) {
+        for (int i = 0; i < w; ++i) incl += wcnt[i];
+        unsigned excl = incl - c;
+        if (excl < need && need <= incl) {
+          ctrl[2] = (unsigned)tid; ctrl[3] = c; ctrl[4] = excl;
+        }
+      }
+      __syncthreads();
+      need -= ctrl[4];
+      kval |= (unsigned long long)ctrl[2] << shift;
+      kmask |= (unsigned long long)dm << shift;
+      if (ctrl[3] == need) break;  // the whole bucket is needed: resolved
+    }
+  }
+
+  // collect (raw key, id) and sort under sel_less
+  each([&](float key, unsigned id) {
+    unsigned long long c = seg_comp(key, id) & kmask;
+    bool take = c < kval;
+    if (c == kval) take = atomicAdd(&ctrl[1], 1u) < need;
+    if (take) {
+      unsigned slot = atomicAdd(&ctrl[0], 1u);
+      if (slot < SEG_KMAX) { outd[slot] = key; outp[slot] = id; }
+    }
+  });
+  __syncthreads();
+  int got = (int)ctrl[0];
+  got = got < k ? got : k;
+  int P = 2;
+  while (P < got) P <<= 1;
+  for (int i = got + tid; i < P; i += SEG_BS) {
+    outd[i] = DFANN_FLT_MAX;
+    outp[i] = PAD_POS;
+  }
+  for (int kk = 2; kk <= P; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < P; i += SEG_BS) {
+        int ixj = i ^ j;
+        if (ixj > i) {
+          bool asc = ((i & kk) == 0);
+          float di = outd[i], dj = outd[ixj];
+          unsigned pi = outp[i], pj = outp[ixj];
+          bool sw = asc ? sel_less(dj, pj, di, pi) : sel_less(di, pi, dj, pj);
+          if (sw) {
+            outd[i] = dj; outd[ixj] = di;
+            outp[i] = pj; outp[ixj] = pi;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = tid; j < k; j += SEG_BS) {
+    bool v = j < got;
+    src.store(q, j, k, v, v ? outd[j] : DFANN_FLT_MAX, v ? outp[j] : PAD_POS);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // encode / build kernels
 // ---------------------------------------------------------------------------
 

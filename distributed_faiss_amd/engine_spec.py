@@ -229,6 +229,7 @@ ENGINE_PERF_KNOBS = (
     "pq_lut_f16",     # fp16 ADC tables (tolerance path)
     "scan_fan",       # list-segment fan (experiment knob)
     "range_max_results",  # range search: largest result, in hits
+    "k_max",          # largest k served, 512..2048 (large-k path above 512)
 )
 
 

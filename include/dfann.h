@@ -22,9 +22,20 @@
  *    ids and applies it inside the scan kernels.
  *
  * Limits (engine caps; the faiss-backed reference has none of these):
- *  - k (top-k) <= 512 everywhere (dfann_search*, dfann_merge_topk):
- *    selection buffers are sized SEL_CAP=1024 with k<=512 headroom.
- *    Larger k returns an error ("k > 512 unsupported").
+ *  - k (top-k) <= 512 by default (dfann_search*): selection buffers are
+ *    sized SEL_CAP=1024 with k<=512 headroom. Larger k returns an error
+ *    ("k > 512 unsupported"). Spec key "k_max" (512..2048, see
+ *    dfann_create) raises the cap of flat / ivf_flat / ivfpq / ivfsq
+ *    indexes without refine: 512 < k <= k_max takes the large-k path
+ *    (DESIGN.md §6l), k <= 512 is served as before, bit for bit, and
+ *    k > k_max is "k > <k_max> unsupported". What the large-k path costs
+ *    on the IVF indexes: it scans the probed lists twice (count pass, fill
+ *    pass), synchronizes the stream twice per query chunk — so it does not
+ *    capture into a HIP graph — and holds every candidate of a query chunk,
+ *    12 bytes each, at most "range_max_results" of them (larger batches are
+ *    split; one query whose probed lists alone hold more is an error naming
+ *    both keys). Flat indexes pay none of that. dfann_merge_topk has no
+ *    index behind it and takes k <= 2048.
  *  - nprobe is clamped to min(nlist, 512). A request above 512 is
  *    honored as 512 and a one-time warning is printed to stderr (the
  *    reference would probe more lists; recall at nprobe=512 is the cap).
@@ -160,6 +171,9 @@ typedef void *dfann_stream;             /* hipStream_t */
  * Errors naming the key: "opq" on another index type, opq_dim > dim,
  * opq_dim % m != 0, and "opq" with "pq_precomputed" (the term2 table is
  * not wired behind the transform).
+ * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
+ * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
+ * together with "refine".
  * Replaces: faiss.IndexFlatIP/IndexFlatL2 (ref index.py:28-30,94),
  * faiss.IndexIVFFlat (ref index.py:38), faiss.IndexIVFPQ (ref
  * index.py:46), faiss.IndexIVFScalarQuantizer + QT_fp16/QT_8bit (ref
@@ -189,8 +203,10 @@ int dfann_add(dfann_index *h, int64_t n, const float *x_dev,
 /* --- search path ------------------------------------------------------ */
 
 /* Replaces faiss `Index.search` at ref index.py:257. D_dev: (nq,k) f32,
- * I_dev: (nq,k) i64. k <= 512 (see Limits above). NaN / Inf query rows:
- * Hostile input, S2 - S4. */
+ * I_dev: (nq,k) i64. k <= k_max (512 unless the spec raises it; above 512
+ * the call synchronizes the stream on an IVF index, see Limits above). The
+ * same holds for the filtered, preassigned and reconstruct entries. NaN /
+ * Inf query rows: Hostile input, S2 - S4. */
 int dfann_search(dfann_index *h, int64_t nq, const float *q_dev, int k,
                  float *D_dev, int64_t *I_dev, dfann_stream stream);
 
@@ -401,7 +417,8 @@ int dfann_get_sq_params(dfann_index *h, float *vmin_host,
  * Output ids are GLOBAL slots s*nq*k + q*k + j into the gathered input
  * (the caller maps slots to (shard, local id) / metadata, mirroring ref
  * client.py:290,297-298). Dout is negated for maximize (ref quirk 2).
- * k <= 512 (see Limits above). */
+ * k <= 2048; k in 513..2048 runs k_select_seg over the S*k slots of a
+ * query, stream-ordered like the smaller k. */
 int dfann_merge_topk(int64_t nq, int S, int k, const float *D_dev,
                      const int64_t *I_dev, int maximize, float *Dout_dev,
                      int64_t *Iout_dev, dfann_stream stream);
