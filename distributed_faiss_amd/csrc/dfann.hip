@@ -106,6 +106,21 @@ static std::string json_str(const std::string &js, const char *key,
   return v;
 }
 
+// the keys of the dict, in order
+static std::vector<std::string> json_keys(const std::string &js) {
+  std::vector<std::string> keys;
+  size_t p = 0;
+  while ((p = js.find('"', p)) != std::string::npos) {
+    size_t e = js.find('"', p + 1);
+    if (e == std::string::npos) break;
+    size_t c = e + 1;
+    while (c < js.size() && (js[c] == ' ' || js[c] == '\t')) ++c;
+    if (c < js.size() && js[c] == ':') keys.push_back(js.substr(p + 1, e - p - 1));
+    p = e + 1;
+  }
+  return keys;
+}
+
 // ---------------------------------------------------------------------------
 // device buffer
 // ---------------------------------------------------------------------------
@@ -280,7 +295,9 @@ static std::vector<int64_t> pick_init(int64_t n, int64_t k, uint64_t seed) {
 // index object
 // ---------------------------------------------------------------------------
 
-enum IdxType { T_FLAT = 0, T_IVFFLAT = 1, T_IVFPQ = 2, T_IVFSQ = 3, T_HNSW = 4 };
+enum IdxType {
+  T_FLAT = 0, T_IVFFLAT = 1, T_IVFPQ = 2, T_IVFSQ = 3, T_HNSW = 4, T_IVFRBQ = 5
+};
 enum { M_IP = 0, M_L2 = 1 };
 
 static int round16(int b) { return (b + 15) & ~15; }
@@ -400,6 +417,9 @@ struct dfann_index {
   int opq_niter = 16;     // spec "opq_niter" (faiss OPQMatrix: 50)
   DevBuf opq_A, opq_At;   // (d_out, d_in) and its transpose, fp32
   DevBuf opq_q, opq_x, opq_r;  // transformed queries / add chunk / decode
+  // ivfrabitq spec "rr" (DESIGN.md §6m): a seeded random rotation, d x d,
+  // kept and applied as the transform above (opq is set with it)
+  bool rr = false;
 
   // timing
   bool timing = false;
@@ -913,6 +933,41 @@ static void opq_polar(double *X, int R, int C, DevBuf &G, DevBuf &T,
   HIP_CHECK(hipStreamSynchronize(stream));
 }
 
+// Seeded Gaussian di x di (SplitMix64 + Box-Muller), orthonormalised by the
+// polar routine: Q (fp64) on return. The start of OPQ's alternation, and the
+// whole of the ivfrabitq rotation.
+static void opq_random_orthonormal(uint64_t seed, int di, DevBuf &Q, DevBuf &G,
+                                   DevBuf &T, DevBuf &scal,
+                                   hipStream_t stream) {
+  std::vector<double> g((size_t)di * di);
+  SplitMix64 rng(seed ^ 0x4F50514D41545258ULL);  // "OPQMATRX"
+  for (size_t i = 0; i < g.size(); i += 2) {
+    double u1 = ((double)(rng.next() >> 11) + 1.0) * (1.0 / 9007199254740992.0);
+    double u2 = (double)(rng.next() >> 11) * (1.0 / 9007199254740992.0);
+    double r = std::sqrt(-2.0 * std::log(u1));
+    g[i] = r * std::cos(6.283185307179586 * u2);
+    if (i + 1 < g.size()) g[i + 1] = r * std::sin(6.283185307179586 * u2);
+  }
+  Q.ensure(g.size() * 8);
+  HIP_CHECK(hipMemcpy(Q.p, g.data(), g.size() * 8, hipMemcpyHostToDevice));
+  opq_polar(Q.as<double>(), di, di, G, T, scal, stream);
+}
+
+// ivfrabitq "rr": A = that matrix as it stands, no learning
+static void rbq_rotation(dfann_index *h, hipStream_t stream) {
+  const int d = h->d;
+  DevBuf Q, G, T, scal;
+  opq_random_orthonormal(h->seed, d, Q, G, T, scal, stream);
+  h->opq_A.ensure((size_t)d * d * 4);
+  h->opq_At.ensure((size_t)d * d * 4);
+  hipLaunchKernelGGL(k_opq_store, grid1d((int64_t)d * d), dim3(256), 0, stream,
+                     Q.as<double>(), d, d, h->opq_A.as<float>(),
+                     h->opq_At.as<float>());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(stream));
+  h->opq_set = true;
+}
+
 // Learn A on the raw training rows (restates faiss OPQMatrix::train):
 // alternate a plain m x ksub PQ on Y = Xc A^T with the orthogonal
 // Procrustes update A^T = polar(Xc^T Yhat).
@@ -934,23 +989,9 @@ static void opq_learn(dfann_index *h, int64_t n, const float *x,
   hipLaunchKernelGGL(k_opq_center, grid1d(nt * di), dim3(256), 0, stream,
                      xc.as<float>(), (long long)nt, di, mean.as<double>());
   HIP_CHECK(hipGetLastError());
-  // 2) seeded Gaussian d_in x d_in (SplitMix64 + Box-Muller), orthonormalised
-  //    by the same polar routine; its first d_out columns are A^T
+  // 2) seeded random orthonormal matrix; its first d_out columns are A^T
   DevBuf Q, P, M, G, T, scal;
-  {
-    std::vector<double> g((size_t)di * di);
-    SplitMix64 rng(h->seed ^ 0x4F50514D41545258ULL);  // "OPQMATRX"
-    for (size_t i = 0; i < g.size(); i += 2) {
-      double u1 = ((double)(rng.next() >> 11) + 1.0) * (1.0 / 9007199254740992.0);
-      double u2 = (double)(rng.next() >> 11) * (1.0 / 9007199254740992.0);
-      double r = std::sqrt(-2.0 * std::log(u1));
-      g[i] = r * std::cos(6.283185307179586 * u2);
-      if (i + 1 < g.size()) g[i + 1] = r * std::sin(6.283185307179586 * u2);
-    }
-    Q.ensure(g.size() * 8);
-    HIP_CHECK(hipMemcpy(Q.p, g.data(), g.size() * 8, hipMemcpyHostToDevice));
-  }
-  opq_polar(Q.as<double>(), di, di, G, T, scal, stream);
+  opq_random_orthonormal(h->seed, di, Q, G, T, scal, stream);
   P.ensure((size_t)di * dout * 8);
   M.ensure((size_t)di * dout * 8);
   hipLaunchKernelGGL(k_opq_take_cols, grid1d((int64_t)di * dout), dim3(256), 0,
@@ -1045,6 +1086,7 @@ static dfann_index *create_from_spec(const std::string &js) {
   else if (t == "ivfpq") h->type = T_IVFPQ;
   else if (t == "ivfsq") h->type = T_IVFSQ;
   else if (t == "hnswsq") h->type = T_HNSW;
+  else if (t == "ivfrabitq") h->type = T_IVFRBQ;
   else { delete h; throw std::runtime_error("unknown index type '" + t + "'"); }
   h->d = (int)json_int(js, "dim", 0);
   h->metric = (int)json_int(js, "metric", M_IP);
@@ -1100,6 +1142,36 @@ static dfann_index *create_from_spec(const std::string &js) {
     delete h;
     throw std::runtime_error("opq_dim given without \"opq\": 1");
   }
+  h->rr = json_int(js, "rr", 0) != 0;
+  if (h->rr && h->type != T_IVFRBQ) {
+    delete h;
+    throw std::runtime_error("\"rr\" unsupported for index type '" + t +
+                             "' (ivfrabitq only)");
+  }
+  if (h->type == T_IVFRBQ) {
+    // nothing is trained beyond the centroids, so a key of another codec
+    // would be dropped silently: every key is checked against the list
+    static const char *const known[] = {
+        "type", "dim", "metric", "nlist", "nprobe", "seed", "rr", "refine",
+        "k_factor", "refine_slab_mb", "ws_mb", "coarse_bf16", "max_ppc",
+        "scan_fan", "range_max_results", "k_max", "merge_mb", "slab_mb"};
+    for (const std::string &key : json_keys(js)) {
+      bool ok = false;
+      for (const char *kn : known) ok = ok || key == kn;
+      if (!ok) {
+        delete h;
+        throw std::runtime_error("ivfrabitq: unknown key \"" + key + "\"");
+      }
+    }
+    if (h->d > RBQ_MAX_D) {
+      int dd = h->d;
+      delete h;
+      throw std::runtime_error(
+          "ivfrabitq dim=" + std::to_string(dd) + " unsupported (the scan's "
+          "table holds at most dim " + std::to_string(RBQ_MAX_D) + ")");
+    }
+    h->opq = h->rr;  // the rotation is the index's transform, d_in == d
+  }
   {
     std::string fs;
     if (json_find(js, "flat_store", fs)) {
@@ -1149,6 +1221,12 @@ static dfann_index *create_from_spec(const std::string &js) {
     h->code_bytes = h->sq_int() ? (h->d * h->sq_bits + 7) / 8 : 2 * h->d;
   } else if (h->type == T_IVFFLAT) {
     h->code_bytes = 4 * h->d;
+  } else if (h->type == T_IVFRBQ) {
+    // one sign bit per dimension, then fp32 n2 and f; the
+    // scan walks the bits as m nibbles
+    h->m = (h->d + 3) / 4;
+    h->dsub = 4;
+    h->code_bytes = rbq_bit_bytes(h->d) + 8;
   } else if (h->type == T_HNSW) {
     // reference index.py:51-60: faiss.IndexHNSWSQ(dim, QT_8bit, store_n)
     // with L2 asserted; spec m = store_n (link cap M), nprobe = efSearch
@@ -1199,10 +1277,10 @@ static dfann_index *create_from_spec(const std::string &js) {
       throw std::runtime_error("unknown refine codec '" + rf +
                                "' (supported: fp32, fp16)");
     }
-    if (h->type != T_IVFPQ && h->type != T_IVFSQ) {
+    if (h->type != T_IVFPQ && h->type != T_IVFSQ && h->type != T_IVFRBQ) {
       delete h;
       throw std::runtime_error("refine unsupported for index type '" + t +
-                               "' (supported bases: ivfpq, ivfsq)");
+                               "' (supported bases: ivfpq, ivfsq, ivfrabitq)");
     }
     h->k_factor = json_float(js, "k_factor", 1.0);
     if (!(h->k_factor >= 1.0)) {
@@ -1454,6 +1532,13 @@ static void encode_chunk(dfann_index *h, int64_t n, const float *x,
   h->pend_arena.ensure_rows(row0 + n);
   uint8_t *const *dst = h->pend_arena.dev_table_mut(stream);
   int rlog = h->pend_arena.rlog;
+  if (h->type == T_IVFRBQ) {  // writes its rows whole, pad included
+    hipLaunchKernelGGL(k_rbq_encode, grid1d((n + 3) / 4, 1), dim3(256), 0,
+                       stream, x, h->centroids.as<float>(), asg, (long long)n,
+                       h->d, h->stride, rlog, (long long)row0, dst);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (h->stride > h->code_bytes)
     hipLaunchKernelGGL(k_zero_row_pad,
                        grid1d(n * (h->stride - h->code_bytes)), dim3(256), 0,
@@ -2167,6 +2252,10 @@ static ScanPlan plan_scan(const dfann_index *h, int k, int nprobe,
                : h->sq_bits == 4 ? SCAN_SQ4
                                  : SCAN_SQF;
       p.fam_floats = h->sq_int() ? 2 * h->d : h->d;
+      break;
+    case T_IVFRBQ:
+      p.mode = SCAN_RBQ;
+      p.fam_floats = RBQ_FAM_FLOATS(h->m);
       break;
     default:
       throw std::runtime_error("scan on flat index");
@@ -3021,7 +3110,10 @@ extern "C" int dfann_train(dfann_index *h, int64_t n, const float *x_dev,
     // faiss IndexPreTransform::train: learn the transform on the raw rows
     // (kept as is when one was injected), then train the inner index on
     // the transformed set
-    if (!h->opq_set) opq_learn(h, n, x_dev, s);
+    if (!h->opq_set) {
+      if (h->rr) rbq_rotation(h, s);
+      else opq_learn(h, n, x_dev, s);
+    }
     DevBuf y;
     y.ensure((size_t)std::max<int64_t>(n, 1) * h->d * 4);
     run_transform(nullptr, h->opq_A.as<float>(), n, x_dev, h->d_in, h->d,
@@ -3231,6 +3323,7 @@ extern "C" int dfann_search_reconstruct(dfann_index *h, int64_t nq,
   else if (h->type == T_IVFFLAT) rtype = 0;
   else if (h->type == T_IVFPQ) rtype = h->nbits == 4 ? 6 : 2;
   else if (h->type == T_HNSW) rtype = 5;
+  else if (h->type == T_IVFRBQ) rtype = 10;
   else
     rtype = h->sq_bits == 8 ? 3 : h->sq_bits == 6 ? 8 : h->sq_bits == 4 ? 7 : 4;
   hipLaunchKernelGGL(k_reconstruct, dim3((unsigned)(nq * k)), dim3(64), 0,

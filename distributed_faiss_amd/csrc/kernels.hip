@@ -1365,32 +1365,17 @@ extern "C" __global__ __launch_bounds__(256) void k_assign_rowblock(
     }                                                                          \
   }
 
-template <int FAM, bool IS_IP, bool L16 = false, bool N4 = false>
-__device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
-                                               const float *__restrict__ fam,
-                                               int d, int m) {
+// Sum of lut[j * 16 + nibble j of the row] over j < m, in ascending j: the
+// row walk of the 4-bit PQ scan and of the RaBitQ scan.
+// 64-byte batches = 128 nibbles; word w is loaded iff it holds a nibble in
+// use (32w < m), and then lies wholly inside the row: the stride is a
+// multiple of 16 above (m + 1) / 2 > 16w.
+__device__ __forceinline__ float nibble_lut_sum(const uint8_t *__restrict__ cp,
+                                                const float *__restrict__ lut,
+                                                int m) {
   float acc = 0.f;
   const uint4 zero4 = {0, 0, 0, 0};
-  if (FAM == 0 && N4) {
-    // 64-byte batches = 128 codes; word w is loaded iff it holds a code
-    // (32w < m), and then lies wholly inside the row: stride is
-    // ceil16((m + 1) / 2) > 16w
-    const float *lut = fam;
-    if ((m & 31) == 0) {  // wave-uniform
-      for (int g0 = 0; g0 < m; g0 += 128) {
-#pragma clang fp contract(off)
-        const uint8_t *rp = cp + (g0 >> 1);
-        uint4 wa = *reinterpret_cast<const uint4 *>(rp);
-        uint4 wb = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(rp + 16) : zero4;
-        uint4 wc = (g0 + 64 < m) ? *reinterpret_cast<const uint4 *>(rp + 32) : zero4;
-        uint4 wd4 = (g0 + 96 < m) ? *reinterpret_cast<const uint4 *>(rp + 48) : zero4;
-        DFANN_PROC32_PQ4_FULL(wa, g0)
-        DFANN_PROC32_PQ4_FULL(wb, g0 + 32)
-        DFANN_PROC32_PQ4_FULL(wc, g0 + 64)
-        DFANN_PROC32_PQ4_FULL(wd4, g0 + 96)
-      }
-      return acc;
-    }
+  if ((m & 31) == 0) {  // wave-uniform
     for (int g0 = 0; g0 < m; g0 += 128) {
 #pragma clang fp contract(off)
       const uint8_t *rp = cp + (g0 >> 1);
@@ -1398,12 +1383,66 @@ __device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
       uint4 wb = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(rp + 16) : zero4;
       uint4 wc = (g0 + 64 < m) ? *reinterpret_cast<const uint4 *>(rp + 32) : zero4;
       uint4 wd4 = (g0 + 96 < m) ? *reinterpret_cast<const uint4 *>(rp + 48) : zero4;
-      DFANN_PROC32_PQ4(wa, g0)
-      DFANN_PROC32_PQ4(wb, g0 + 32)
-      DFANN_PROC32_PQ4(wc, g0 + 64)
-      DFANN_PROC32_PQ4(wd4, g0 + 96)
+      DFANN_PROC32_PQ4_FULL(wa, g0)
+      DFANN_PROC32_PQ4_FULL(wb, g0 + 32)
+      DFANN_PROC32_PQ4_FULL(wc, g0 + 64)
+      DFANN_PROC32_PQ4_FULL(wd4, g0 + 96)
     }
-  } else if (FAM == 0) {
+    return acc;
+  }
+  for (int g0 = 0; g0 < m; g0 += 128) {
+#pragma clang fp contract(off)
+    const uint8_t *rp = cp + (g0 >> 1);
+    uint4 wa = *reinterpret_cast<const uint4 *>(rp);
+    uint4 wb = (g0 + 32 < m) ? *reinterpret_cast<const uint4 *>(rp + 16) : zero4;
+    uint4 wc = (g0 + 64 < m) ? *reinterpret_cast<const uint4 *>(rp + 32) : zero4;
+    uint4 wd4 = (g0 + 96 < m) ? *reinterpret_cast<const uint4 *>(rp + 48) : zero4;
+    DFANN_PROC32_PQ4(wa, g0)
+    DFANN_PROC32_PQ4(wb, g0 + 32)
+    DFANN_PROC32_PQ4(wc, g0 + 64)
+    DFANN_PROC32_PQ4(wd4, g0 + 96)
+  }
+  return acc;
+}
+
+// RaBitQ rows: fb bit bytes, then fp32 n2 = |r|^2 and
+// f = |r|^2 / |r|_1. The scan's LDS region is the subset-sum table
+// (16 floats per nibble), then S and qn2, then the staged v.
+__host__ __device__ __forceinline__ int rbq_bit_bytes(int d) {
+  return (((d + 7) >> 3) + 3) & ~3;
+}
+#define RBQ_MAX_D 2048
+// The RaBitQ kernels are compiled without the packed fp32 instructions
+// (v_pk_add_f32 and kin): their sums are scalar fp32 in a stated order.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DFANN_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DFANN_NO_PK_F32
+#endif
+#define RBQ_FAM_FLOATS(M) (20 * (M) + 4)
+
+template <int FAM, bool IS_IP, bool L16 = false, bool N4 = false>
+__device__ __forceinline__ float scan_row_dist(const uint8_t *__restrict__ cp,
+                                               const float *__restrict__ fam,
+                                               int d, int m) {
+  float acc = 0.f;
+  const uint4 zero4 = {0, 0, 0, 0};
+  if (FAM == 4) {
+    // <r, v> ~ f * (2B - S), B the sum of v over the row's set bits. n2 and
+    // f are loaded before the walk, so they travel with its first batch.
+    const int fb = rbq_bit_bytes(d);
+    const float n2 = *reinterpret_cast<const float *>(cp + fb);
+    const float f = *reinterpret_cast<const float *>(cp + fb + 4);
+    const float B = nibble_lut_sum(cp, fam, m);
+    {
+#pragma clang fp contract(off)
+      const float S = fam[m * 16], qn2 = fam[m * 16 + 1];
+      float est = f * ((B + B) - S);
+      return IS_IP ? est : (n2 + qn2) - (est + est);
+    }
+  }
+  if (FAM == 0 && N4) return nibble_lut_sum(cp, fam, m);
+  if (FAM == 0) {
     using LT = typename std::conditional<L16, __half, float>::type;
     const LT *lut = reinterpret_cast<const LT *>(fam);
     if ((m & 15) == 0) {  // wave-uniform
@@ -1803,6 +1842,54 @@ __device__ void ivf_scan_body(
         vbuf[t] = sct;
       }
     }
+  } else if (FAM == 4) {
+    // RaBitQ: v = q (IP) or q - c (L2), zero past d, staged
+    // behind the table; then S = sum v and qn2 = sum v^2, and the subset-sum
+    // table lut[j * 16 + c] = sum of v[4j + b] over the bits b of c. Nothing
+    // here depends on the block size: the sums are wave 0's, lane l adding
+    // t = l, l + 64, ... in ascending order, then a fixed xor butterfly
+    // (32 .. 1); a table row is filled by doubling, b ascending, so each
+    // entry is a sum in ascending b.
+    float *lut = fam, *sums = fam + (size_t)m * 16, *vb = sums + 4;
+    for (int t = threadIdx.x; t < 4 * m; t += blockDim.x) {
+      float v = 0.f;
+      if (t < d) v = IS_IP ? qp[t] : qp[t] - cent[(long long)L * d + t];
+      vb[t] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+#pragma clang fp contract(off)
+      float s = 0.f, n = 0.f;
+      for (int t = threadIdx.x; t < d; t += 64) {
+        float v = vb[t];
+        s = s + v;
+        n = n + v * v;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        s = s + __shfl_xor(s, o);
+        n = n + __shfl_xor(n, o);
+      }
+      if (threadIdx.x == 0) {
+        sums[0] = s;
+        sums[1] = n;
+      }
+    }
+    for (int j = threadIdx.x; j < m; j += blockDim.x) {
+#pragma clang fp contract(off)
+      const float4 v4 = *reinterpret_cast<const float4 *>(vb + 4 * j);
+      const float vv[4] = {v4.x, v4.y, v4.z, v4.w};
+      float e[16];
+      e[0] = 0.f;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int c = 0; c < (1 << b); ++c) e[c | (1 << b)] = e[c] + vv[b];
+      float4 *row = reinterpret_cast<float4 *>(lut + 16 * j);
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        row[w] = make_float4(e[4 * w], e[4 * w + 1], e[4 * w + 2], e[4 * w + 3]);
+    }
   } else {  // SQfp16
     for (int t = threadIdx.x; t < d; t += blockDim.x)
       fam[t] = IS_IP ? qp[t] : qp[t] - cent[(long long)L * d + t];
@@ -2152,6 +2239,8 @@ __device__ void ivf_scan_body(
 //   GLUT: LUT staged from HBM (built by k_pq_lut) instead of computed in
 //         the scan prologue; L16: those rows are __half (pq_lut_f16)
 //   N4:   4-bit PQ (nbits=4), in-kernel fp32 LUT only
+//   FAM:  0 PQ LUT, 1 raw fp32, 2 integer SQ, 3 SQ fp16, 4 RaBitQ (§6m:
+//         subset-sum LUT over the row's sign bits + per-row affine epilogue)
 //   SQB:  bits per dimension of an integer SQ row (FAM 2): 8, or the
 //         packed 6 / 4; 8 on every other row, unread
 // _rg[_f]: range mode (RANGE=true). One kernel serves the
@@ -2212,11 +2301,19 @@ __device__ __forceinline__ void scan_entry(const ScanArgs &a) {
   X(SQ8, sq8, , 2, false, false, false, false, 8)                              \
   X(SQ6, sq6, , 2, false, false, false, false, 6)    /* packed 6-bit SQ */     \
   X(SQ4, sq4, , 2, false, false, false, false, 4)    /* packed 4-bit SQ */     \
-  X(SQF, sqf, , 3, false, false, false, false, 8)    /* SQ fp16 */
+  X(SQF, sqf, , 3, false, false, false, false, 8)    /* SQ fp16 */             \
+  X(RBQ, rbq, , 4, false, false, false, false, 8)    /* RaBitQ 1-bit */
 
+// per-family kernel attribute
+#define DFANN_SCAN_ATTR_0
+#define DFANN_SCAN_ATTR_1
+#define DFANN_SCAN_ATTR_2
+#define DFANN_SCAN_ATTR_3
+#define DFANN_SCAN_ATTR_4 DFANN_NO_PK_F32
 #define DFANN_SCAN_KERNEL(KNAME, FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, \
                           RANGE, SQB)                                          \
-  extern "C" __global__ __launch_bounds__(512) void KNAME(ScanArgs a) {        \
+  extern "C" __global__ DFANN_SCAN_ATTR_##FAM __launch_bounds__(512) void      \
+  KNAME(ScanArgs a) {                                                          \
     scan_entry<FAM, IS_IP, REGSEL, PRE, GLUT, L16, N4, FILT, RANGE, SQB>(a);   \
   }
 #define DFANN_SCAN_METRIC(NAME, MET, SUFFIX, FAM, IS_IP, PRE, GLUT, L16, N4,   \
@@ -3449,6 +3546,54 @@ extern "C" __global__ void k_zero_row_pad(long long n, int code_bytes,
     slab_row_mut(out, rlog, row0 + i / pad, stride)[code_bytes + i % pad] = 0;
 }
 
+// RaBitQ encode: one wave per row, four rows per block.
+// Step s covers dimensions 64s + lane: r = x - c (one subtraction), the
+// 64-lane ballot of r > 0 is the row's bits 64s .. 64s + 63, stored as two
+// dwords by lanes 0 and 1 (only dwords below fb; a lane past d votes 0, so
+// bits at or past d are 0). Each lane keeps sequential partials of r^2 and
+// |r| over its steps; a fixed xor butterfly (32 .. 1) combines them. Then
+// n2 at byte fb, f = n2 / |r|_1 (0 when |r|_1 is 0) at fb + 4 and zero up
+// to the stride. Every byte of the row is written, with plain vector
+// stores; no atomics.
+extern "C" __global__ DFANN_NO_PK_F32 __launch_bounds__(256) void k_rbq_encode(
+    const float *__restrict__ x, const float *__restrict__ cent,
+    const int *__restrict__ asg, long long n, int d, int stride, int rlog,
+    long long row0, uint8_t *const *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int fb = rbq_bit_bytes(d);
+  for (long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); row < n;
+       row += (long long)gridDim.x * 4) {
+    const float *xp = x + row * d;
+    const float *cp = cent + (long long)asg[row] * d;
+    uint8_t *rp = slab_row_mut(out, rlog, row0 + row, stride);
+    unsigned *rw = reinterpret_cast<unsigned *>(rp);
+    float s2 = 0.f, s1 = 0.f;
+    for (int t0 = 0; t0 < d; t0 += 64) {
+#pragma clang fp contract(off)
+      const int t = t0 + lane;
+      const float r = t < d ? xp[t] - cp[t] : 0.f;
+      s2 = s2 + r * r;
+      s1 = s1 + fabsf(r);
+      const unsigned long long bits = __ballot(r > 0.f);
+      const int w = (t0 >> 5) + lane;  // lanes 0, 1: the step's two dwords
+      if (lane < 2 && 4 * w < fb) rw[w] = (unsigned)(bits >> (32 * lane));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+      s2 = s2 + __shfl_xor(s2, o);
+      s1 = s1 + __shfl_xor(s1, o);
+    }
+    const int tail = fb + 4 * lane;  // n2, f, then the pad dwords
+    if (tail < stride) {
+      float v = 0.f;
+      if (lane == 0) v = s2;
+      if (lane == 1) v = s1 > 0.f ? s2 / s1 : 0.f;
+      *reinterpret_cast<float *>(rp + tail) = v;
+    }
+  }
+}
+
 // two-source CSR rebuild gather (DESIGN.md §2 memory plan): new CSR row j
 // of list l is either an OLD CSR row (same list order) or a PENDING row
 // (arrival order within the list, via the psrc permutation). Both source
@@ -3745,7 +3890,8 @@ extern "C" __global__ void k_minmax_decode(const unsigned *mn, const unsigned *m
 // type: 0 flat/ivfflat raw (flat_src != null uses flat arena directly by id,
 // else CSR codes row), 2 pq, 3 sq8, 4 sqfp16, 5 hnsw sq8, 6 pq nbits=4,
 // 7 sq4, 8 sq6 (packed bit streams), 9 flat fp16 rows
-// (flat_src holds them, `stride` bytes apart)
+// (flat_src holds them, `stride` bytes apart), 10 RaBitQ
+// sign bits with the row's least-squares scale
 // ---------------------------------------------------------------------------
 
 extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
@@ -3833,6 +3979,13 @@ extern "C" __global__ __launch_bounds__(64) void k_reconstruct(
       unsigned c = (w >> sh) & 63u;
       out[t] = cent[(long long)L * d + t] + (vmin[t] + ((float)c + 0.5f) * scale[t]);
     }
+  } else if (type == 10) {  // RaBitQ: c + s * a, a = n2 / (f d) = |r|_1 / d
+    const int fb = rbq_bit_bytes(d);
+    const float n2 = *reinterpret_cast<const float *>(cp + fb);
+    const float f = *reinterpret_cast<const float *>(cp + fb + 4);
+    const float a = f != 0.f ? n2 / (f * (float)d) : 0.f;
+    for (int t = threadIdx.x; t < d; t += blockDim.x)
+      out[t] = cent[(long long)L * d + t] + (((cp[t >> 3] >> (t & 7)) & 1) ? a : -a);
   } else {  // sqfp16
     const unsigned short *hp = reinterpret_cast<const unsigned short *>(cp);
     for (int t = threadIdx.x; t < d; t += blockDim.x) {

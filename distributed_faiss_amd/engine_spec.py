@@ -5,13 +5,15 @@
 # :497-508 infer_n_centroids) as a backend-neutral spec dict consumed by
 # both the HIP engine (distributed_faiss_amd/hip_engine.py) and the test
 # oracle. Engine spec keys:
-#   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq"
+#   type:    "flat" | "ivf_flat" | "ivfpq" | "ivfsq" | "ivfrabitq"
 #   dim, metric (0=IP, 1=L2), nlist, m, nbits (ivfpq: 4 | 8; DESIGN.md
 #   §6d), flat_store ("fp32"|"fp16", flat only), sq_type ("fp16"|"8bit"|"6bit"|"4bit"), nprobe, seed
 #   refine ("fp32"|"fp16"), k_factor: exact re-ranking over ivfpq / ivfsq
 #   (faiss IndexRefineFlat / IndexRefine)
 #   opq (1), opq_dim, opq_niter: learned orthonormal pre-transform in front
 #   of ivfpq (faiss IndexPreTransform(OPQMatrix))
+#   rr (1): seeded random rotation in front of ivfrabitq (faiss
+#   IndexIVFRaBitQ with an "RR" pre-transform)
 #
 # Behavioral quirks kept on purpose (SURVEY.md §2 quirk list):
 #   * builder "flat" ALWAYS builds an inner-product flat index, ignoring
@@ -112,6 +114,10 @@ _FACTORY_RE = re.compile(
     r"IVF(\d+),(?:(Flat)|(PQ(\d+)(?:x(\d+))?|SQ8|SQ6|SQ4|SQfp16)"
     r"(?:,(RFlat|Refine\(SQfp16\)))?)$")
 _FACTORY_REFINE = {"RFlat": "fp32", "Refine(SQfp16)": "fp16"}
+# faiss IndexIVFRaBitQ: "IVFn,RaBitQ", optional "RR," in front (a d x d random
+# rotation) and the refine forms behind
+_FACTORY_RBQ_RE = re.compile(
+    r"^(RR,)?IVF(\d+),RaBitQ(?:,(RFlat|Refine\(SQfp16\)))?$")
 # faiss QT_8bit / QT_6bit / QT_4bit / QT_fp16 -> engine "sq_type"
 _FACTORY_SQ = {"SQ8": "8bit", "SQ6": "6bit", "SQ4": "4bit", "SQfp16": "fp16"}
 # "PQ<m>x<b>": bits per sub-quantizer code; "PQ<m>" is faiss's default 8
@@ -166,6 +172,16 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
     if s == "SQfp16":
         spec.update(type="flat", flat_store="fp16")
         return spec
+    rb = _FACTORY_RBQ_RE.match(s)
+    if rb:
+        spec.update(type="ivfrabitq", nlist=int(rb.group(2)))
+        if rb.group(1):
+            spec["rr"] = 1
+        if rb.group(3):
+            spec["refine"] = _FACTORY_REFINE[rb.group(3)]
+            if "k_factor" in cfg.extra:
+                spec["k_factor"] = float(cfg.extra["k_factor"])
+        return spec
     mm = _FACTORY_RE.match(s)
     if not mm:
         raise NotImplementedError(
@@ -173,7 +189,9 @@ def _factory_spec(cfg: IndexCfg, total_data_size: int) -> dict:
             "IVFn,PQm, IVFn,PQmx4, IVFn,PQmx8, IVFn,SQ8, IVFn,SQ6, IVFn,SQ4, "
             "IVFn,SQfp16, "
             "the PQ / SQ forms followed by ,RFlat or ,Refine(SQfp16), and "
-            "the PQ forms preceded by OPQm, or OPQm_d, (same m)"
+            "the PQ forms preceded by OPQm, or OPQm_d, (same m), "
+            "IVFn,RaBitQ, RR,IVFn,RaBitQ and both followed by ,RFlat or "
+            ",Refine(SQfp16)"
         )
     opq_m = mm.group("opq_m")
     nlist = int(mm.group(3))

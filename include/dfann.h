@@ -121,7 +121,7 @@ typedef void *dfann_stream;             /* hipStream_t */
 /* --- lifecycle -------------------------------------------------------- */
 
 /* Build an index from a JSON spec {"type": "flat"|"ivf_flat"|"ivfpq"|
- * "ivfsq", "dim": int, "metric": 0|1, "nlist": int, "m": int,
+ * "ivfsq"|"ivfrabitq", "dim": int, "metric": 0|1, "nlist": int, "m": int,
  * "nbits": 4|8, "sq_type": "fp16"|"8bit"|"6bit"|"4bit", "nprobe": int,
  * "seed": int}.
  * "slab_mb" (ivf types; default 64, clamped to 1..4096): size of the slabs
@@ -158,7 +158,7 @@ typedef void *dfann_stream;             /* hipStream_t */
  * word. Rows are padded to a multiple of 16 bytes (dfann_code_stride);
  * every bit past dim * B, pad bytes included, is zero. "hnswsq" is always
  * 8-bit.
- * Refine stage, "ivfpq" / "ivfsq" only (faiss IndexRefineFlat /
+ * Refine stage, "ivfpq" / "ivfsq" / "ivfrabitq" only (faiss IndexRefineFlat /
  * IndexRefine(SQfp16)): "refine": "fp32"|"fp16" (absent or
  * "" = off) keeps every added vector raw (round16(dim * 4 or 2) bytes per
  * row) and re-ranks the base stage's k' candidates exactly; "k_factor":
@@ -171,6 +171,24 @@ typedef void *dfann_stream;             /* hipStream_t */
  * Errors naming the key: "opq" on another index type, opq_dim > dim,
  * opq_dim % m != 0, and "opq" with "pq_precomputed" (the term2 table is
  * not wired behind the transform).
+ * "ivfrabitq" (faiss IndexIVFRaBitQ): keys "dim" (at most
+ * 2048; above it an error naming the limit), "metric", "nlist", "nprobe",
+ * "seed", "rr", "refine" / "k_factor" / "refine_slab_mb" and the engine knobs
+ * "ws_mb", "coarse_bf16", "max_ppc", "scan_fan", "range_max_results",
+ * "k_max", "merge_mb", "slab_mb"; any other key is an error naming it.
+ * Nothing is trained beyond the coarse centroids (dfann_set_trained takes
+ * only them). With r = x - c (the assigned centroid, one fp32 subtraction)
+ * a row is a little-endian bit stream, bit i = (r_i > 0) in byte i >> 3 at
+ * bit i & 7, bits at or past dim zero, fb = round_up(ceil(dim / 8), 4)
+ * bytes; then fp32 n2 = |r|^2 at byte fb and fp32 f = |r|^2 / |r|_1 (0 when
+ * |r|_1 is 0) at byte fb + 4; zero pad to a multiple of 16 bytes
+ * (dfann_code_stride). <r, v> is estimated as f * sum_i s_i v_i with s_i =
+ * +-1 the stored sign: L2 returns (n2 + |q - c|^2) - 2 f sum s_i (q - c)_i,
+ * IP returns <q, c> + f sum s_i q_i. dfann_search_reconstruct decodes
+ * c_i + s_i * n2 / (f * dim). "rr": 1 puts a seeded random rotation A
+ * (dim x dim, orthonormal) in front, generated at train and handled by the
+ * transform calls below exactly like an "opq" matrix with opq_dim == dim;
+ * "rr" on another index type is an error naming the key.
  * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
  * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
  * together with "refine".
