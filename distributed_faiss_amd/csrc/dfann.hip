@@ -156,6 +156,10 @@ struct DevBuf {
     p = nullptr;
     cap = 0;
   }
+  void swap(DevBuf &o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
   template <typename T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
@@ -313,6 +317,16 @@ struct TimingEv {
   hipEvent_t a, b;
 };
 
+// One lane of the pipelined IVF search (DESIGN.md §3 "Search pipeline"): a
+// non-blocking stream, its join event, and its own copy of every workspace
+// the per-chunk search writes (the fields of the same names in the index).
+static const int PIPE_LANES_MAX = 2;
+struct PipeLane {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr;
+  DevBuf ws1, ws2, ws3, ws4, ws_bf16a, pq_lut_ws, qn_ws, term3_ws;
+};
+
 struct dfann_index {
   std::string spec_json;
   int type = T_FLAT;
@@ -420,6 +434,13 @@ struct dfann_index {
   // ivfrabitq spec "rr" (DESIGN.md §6m): a seeded random rotation, d x d,
   // kept and applied as the transform above (opq is set with it)
   bool rr = false;
+  // search pipeline: spec "pipe_lanes" (-1 auto, 1 serial,
+  // 2) and "pipe_chunk" (queries per chunk, 0 auto); the lanes are made
+  // by the first pipelined call (pipe_lanes_init)
+  int pipe_lanes = -1;
+  int64_t pipe_chunk = 0;
+  PipeLane lanes[PIPE_LANES_MAX];
+  hipEvent_t pipe_fork = nullptr;
 
   // timing
   bool timing = false;
@@ -432,6 +453,16 @@ struct dfann_index {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
       }
+    // the lanes' work was joined onto a caller's stream; drain them before
+    // their workspaces go
+    for (PipeLane &l : lanes) {
+      if (l.stream) {
+        (void)hipStreamSynchronize(l.stream);
+        (void)hipStreamDestroy(l.stream);
+      }
+      if (l.done) (void)hipEventDestroy(l.done);
+    }
+    if (pipe_fork) (void)hipEventDestroy(pipe_fork);
   }
 
   TimingEv ev_begin(hipStream_t s) {
@@ -535,11 +566,15 @@ static dim3 grid1d(int64_t total, int block = 256, int64_t cap = 65535LL * 8) {
 // C[i][j] keys for rows of A vs rows of B under `metric`.
 // mode: 0 -ip, 1 bn-2ip, 2 qn+bn-2ip (needs qn). Result in `keys` (rows x N).
 // B_bf16: pre-converted B for the approximate bf16 path (used only when
-// h->coarse_bf16 and the caller provides it).
+// h->coarse_bf16 and the caller provides it). sel_rows: the row count the
+// bf16 kernel is chosen by, for rows that are a chunk of a larger batch
+// (0: Mrows).
 static void gemm_keys_b(dfann_index *h, const float *A, int64_t Mrows,
                         const float *B, const unsigned short *B_bf16,
                         int64_t N, int K, const float *bn, const float *qn,
-                        int mode, float *keys, hipStream_t stream) {
+                        int mode, float *keys, hipStream_t stream,
+                        int64_t sel_rows = 0) {
+  if (sel_rows < Mrows) sel_rows = Mrows;
   dim3 g((unsigned)((N + GT - 1) / GT), (unsigned)((Mrows + GT - 1) / GT));
   TimingEv e;
   if (h && h->timing) e = h->ev_begin(stream);
@@ -547,7 +582,7 @@ static void gemm_keys_b(dfann_index *h, const float *A, int64_t Mrows,
     h->ws_bf16a.ensure((size_t)Mrows * K * 2);
     hipLaunchKernelGGL(k_f32_to_bf16, grid1d(Mrows * K), dim3(256), 0, stream,
                        A, Mrows * K, h->ws_bf16a.as<unsigned short>());
-    if (K % 8 == 0 && N >= 2048 && Mrows >= 256 && K >= 64) {
+    if (K % 8 == 0 && N >= 2048 && sel_rows >= 256 && K >= 64) {
       // big coarse/assign shapes: 256^2-tile glds kernel (512 threads)
       dim3 g2((unsigned)((N + 255) / 256), (unsigned)((Mrows + 255) / 256));
       hipLaunchKernelGGL(k_gemm_bf16_256, g2, dim3(512), 0, stream,
@@ -1111,6 +1146,9 @@ static dfann_index *create_from_spec(const std::string &js) {
   h->scan_fan = (int)json_int(js, "scan_fan", 1);
   if (h->scan_fan < 1) h->scan_fan = 1;
   if (h->scan_fan > 16) h->scan_fan = 16;
+  h->pipe_lanes = (int)json_int(js, "pipe_lanes", -1);
+  if (h->pipe_lanes > PIPE_LANES_MAX) h->pipe_lanes = PIPE_LANES_MAX;
+  h->pipe_chunk = std::max<int64_t>(0, json_int(js, "pipe_chunk", 0));
   h->range_max = json_int(js, "range_max_results", 1LL << 27);
   if (h->range_max < 0) throw std::runtime_error("range_max_results must be >= 0");
   if (h->d <= 0) { delete h; throw std::runtime_error("bad dim"); }
@@ -1154,7 +1192,8 @@ static dfann_index *create_from_spec(const std::string &js) {
     static const char *const known[] = {
         "type", "dim", "metric", "nlist", "nprobe", "seed", "rr", "refine",
         "k_factor", "refine_slab_mb", "ws_mb", "coarse_bf16", "max_ppc",
-        "scan_fan", "range_max_results", "k_max", "merge_mb", "slab_mb"};
+        "scan_fan", "range_max_results", "k_max", "merge_mb", "slab_mb",
+        "pipe_lanes", "pipe_chunk"};
     for (const std::string &key : json_keys(js)) {
       bool ok = false;
       for (const char *kn : known) ok = ok || key == kn;
@@ -2138,9 +2177,13 @@ static void coarse_fused(dfann_index *h, int64_t nq, const float *q,
   HIP_CHECK(hipGetLastError());
 }
 
+// batch_rows: these nq rows are a chunk of a batch of that many (0: nq).
+// The kernels are the ones the whole batch takes, so a chunk's results are
+// the batch's bit for bit.
 static void coarse_impl(dfann_index *h, int64_t nq, const float *q, int nprobe,
-                        int32_t *probes, float *keys, hipStream_t stream) {
-  if (coarse_fused_ok(h, nq, nprobe)) {
+                        int32_t *probes, float *keys, hipStream_t stream,
+                        int64_t batch_rows = 0) {
+  if (coarse_fused_ok(h, std::max(batch_rows, nq), nprobe)) {
     coarse_fused(h, nq, q, nprobe, probes, keys, stream);
     return;
   }
@@ -2154,7 +2197,7 @@ static void coarse_impl(dfann_index *h, int64_t nq, const float *q, int nprobe,
     gemm_keys_b(h, q + s * h->d, c, h->centroids.as<float>(),
                 h->cent_bf16.as<unsigned short>(), nlist, h->d,
                 h->cnorm.as<float>(), nullptr, h->metric == M_IP ? 0 : 1, sc,
-                stream);
+                stream, batch_rows);
     // 256 measured best (128 is -3%: this kernel is one streaming
     // phase — no phase diversity to recover, unlike the scans)
     unsigned tk_bs = 256;
@@ -2873,6 +2916,102 @@ static void check_preassigned(const dfann_index *h, int k, int nprobe) {
         std::to_string(nprobe) + ")");
 }
 
+// Coarse select, scan and merge of nq query rows on one stream, with the
+// workspaces in the index's slots. batch_rows: see coarse_impl.
+static void search_chunk(dfann_index *h, int64_t nq, const float *q,
+                         int nprobe, int k, float *D, int64_t *I,
+                         hipStream_t stream, const uint32_t *allow,
+                         int64_t batch_rows) {
+  // probes + keys
+  DevBuf &pb = h->ws2;
+  pb.ensure((size_t)nq * nprobe * 8);
+  int32_t *probes = pb.as<int32_t>();
+  float *keys = reinterpret_cast<float *>(pb.as<uint8_t>() + (size_t)nq * nprobe * 4);
+  coarse_impl(h, nq, q, nprobe, probes, keys, stream, batch_rows);
+  scan_and_merge(h, nq, q, nprobe, probes, keys, k, D, I, stream, allow);
+}
+
+// ---------------------------------------------------------------------------
+// Search pipeline: the unfiltered IVF top-k search cut into
+// query chunks that go round-robin over stream lanes, so that one chunk's
+// coarse GEMM (MFMA) and LUT build (VALU) run while another chunk's scan
+// waits on memory. Every stage is independent per query row: a chunk
+// computes the bits the whole batch computes.
+// ---------------------------------------------------------------------------
+
+struct PipePlan {
+  int lanes;      // < 2: the serial path
+  int64_t chunk;  // query rows per chunk
+};
+static const int64_t PIPE_CHUNK_AUTO = 2560;
+
+// Spec "pipe_lanes" / "pipe_chunk"; DFANN_PIPE_LANES / DFANN_PIPE_CHUNK (A/B
+// knobs, read per call) override them. An explicit chunk is used as given.
+// Serial whatever is asked: filtered search, the large-k path, and a call
+// with timing on (its per-stage event buckets are defined on one stream).
+static PipePlan plan_pipe(const dfann_index *h, int64_t nq, int k, int nprobe,
+                          const uint32_t *allow) {
+  int lanes = h->pipe_lanes;
+  if (const char *e = getenv("DFANN_PIPE_LANES"))  // experiment override
+    lanes = atoi(e);
+  int64_t chunk = h->pipe_chunk;
+  if (const char *e = getenv("DFANN_PIPE_CHUNK"))  // experiment override
+    chunk = atoll(e);
+  if (allow || k > K_SEL_MAX || h->timing || lanes == 0 || lanes == 1)
+    return {1, nq};
+  const ScanPlan sp = plan_scan(h, k, nprobe);
+  if (lanes < 0) {
+    // auto: the shapes the gain was measured on (BASELINE.md "Search
+    // pipeline") — fp16 GLUT scan behind the fused bf16 coarse select
+    if (sp.mode != SCAN_PQ_GH || !coarse_fused_ok(h, nq, nprobe))
+      return {1, nq};
+    lanes = 2;
+  }
+  lanes = std::min(lanes, PIPE_LANES_MAX);
+  // auto: a multiple of 256 rows (full M tiles of the coarse GEMM)
+  if (chunk < 1) chunk = PIPE_CHUNK_AUTO;
+  if ((nq + chunk - 1) / chunk < 2) return {1, nq};
+  return {lanes, chunk};
+}
+
+// First pipelined call of the index: an un-captured warm-up call, as the
+// workspace allocations of every first call already require.
+static void pipe_lanes_init(dfann_index *h, int lanes, hipStream_t stream) {
+  if (h->pipe_fork && h->lanes[lanes - 1].stream) return;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_CHECK(hipStreamIsCapturing(stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    throw std::runtime_error(
+        "pipelined search: the first call must not be under stream capture");
+  if (!h->pipe_fork)
+    HIP_CHECK(hipEventCreateWithFlags(&h->pipe_fork, hipEventDisableTiming));
+  for (int l = 0; l < lanes; ++l) {
+    PipeLane &ln = h->lanes[l];
+    if (ln.stream) continue;
+    HIP_CHECK(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+    HIP_CHECK(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+  }
+}
+
+// The lane's workspaces stand in the index's slots while a chunk is issued,
+// so the per-chunk code is the serial path's own.
+struct LaneScope {
+  dfann_index *h;
+  PipeLane &l;
+  LaneScope(dfann_index *h_, PipeLane &l_) : h(h_), l(l_) { swap(); }
+  ~LaneScope() { swap(); }
+  void swap() {
+    h->ws1.swap(l.ws1);
+    h->ws2.swap(l.ws2);
+    h->ws3.swap(l.ws3);
+    h->ws4.swap(l.ws4);
+    h->ws_bf16a.swap(l.ws_bf16a);
+    h->pq_lut_ws.swap(l.pq_lut_ws);
+    h->qn_ws.swap(l.qn_ws);
+    h->term3_ws.swap(l.term3_ws);
+  }
+};
+
 static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
                         float *D, int64_t *I, hipStream_t stream,
                         const uint32_t *allow = nullptr) {
@@ -2901,13 +3040,28 @@ static void search_impl(dfann_index *h, int64_t nq, const float *q, int k,
     }
     nprobe = 512;
   }
-  // probes + keys
-  DevBuf &pb = h->ws2;
-  pb.ensure((size_t)nq * nprobe * 8);
-  int32_t *probes = pb.as<int32_t>();
-  float *keys = reinterpret_cast<float *>(pb.as<uint8_t>() + (size_t)nq * nprobe * 4);
-  coarse_impl(h, nq, q, nprobe, probes, keys, stream);
-  scan_and_merge(h, nq, q, nprobe, probes, keys, k, D, I, stream, allow);
+  const PipePlan pp = plan_pipe(h, nq, k, nprobe, allow);
+  if (pp.lanes < 2) {
+    search_chunk(h, nq, q, nprobe, k, D, I, stream, allow, 0);
+    return;
+  }
+  pipe_lanes_init(h, pp.lanes, stream);
+  // pre-fork, on the caller's stream: everything that writes index state
+  // (finalize_csr above, the slab-table upload here). The lanes only read it.
+  h->csr_arena.dev_table(stream);
+  HIP_CHECK(hipEventRecord(h->pipe_fork, stream));
+  for (int l = 0; l < pp.lanes; ++l)
+    HIP_CHECK(hipStreamWaitEvent(h->lanes[l].stream, h->pipe_fork, 0));
+  int l = 0;
+  for (int64_t q0 = 0; q0 < nq; q0 += pp.chunk, l = (l + 1) % pp.lanes) {
+    LaneScope scope(h, h->lanes[l]);
+    search_chunk(h, std::min(pp.chunk, nq - q0), q + q0 * h->d, nprobe, k,
+                 D + q0 * k, I + q0 * k, h->lanes[l].stream, nullptr, nq);
+  }
+  for (int j = 0; j < pp.lanes; ++j) {
+    HIP_CHECK(hipEventRecord(h->lanes[j].done, h->lanes[j].stream));
+    HIP_CHECK(hipStreamWaitEvent(stream, h->lanes[j].done, 0));
+  }
 }
 
 // ---------------------------------------------------------------------------

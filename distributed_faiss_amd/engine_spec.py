@@ -248,6 +248,8 @@ ENGINE_PERF_KNOBS = (
     "scan_fan",       # list-segment fan (experiment knob)
     "range_max_results",  # range search: largest result, in hits
     "k_max",          # largest k served, 512..2048 (large-k path above 512)
+    "pipe_lanes",     # IVF search pipeline: stream lanes (-1 auto, 1 serial)
+    "pipe_chunk",     # IVF search pipeline: queries per chunk (0 auto)
 )
 
 

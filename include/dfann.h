@@ -175,7 +175,8 @@ typedef void *dfann_stream;             /* hipStream_t */
  * 2048; above it an error naming the limit), "metric", "nlist", "nprobe",
  * "seed", "rr", "refine" / "k_factor" / "refine_slab_mb" and the engine knobs
  * "ws_mb", "coarse_bf16", "max_ppc", "scan_fan", "range_max_results",
- * "k_max", "merge_mb", "slab_mb"; any other key is an error naming it.
+ * "k_max", "merge_mb", "slab_mb", "pipe_lanes", "pipe_chunk"; any other key
+ * is an error naming it.
  * Nothing is trained beyond the coarse centroids (dfann_set_trained takes
  * only them). With r = x - c (the assigned centroid, one fp32 subtraction)
  * a row is a little-endian bit stream, bit i = (r_i > 0) in byte i >> 3 at
