@@ -15,6 +15,7 @@
 
 #include "kernels.hip"
 #include "hnsw.hip"
+#include "scan_group.hip"
 
 #include <cstdio>
 #include <cstdlib>
@@ -366,6 +367,11 @@ struct dfann_index {
                             // parity contract.
   int scan_fan = 1;  // spec "scan_fan": list-segment fan, clamped to
                      // 1..16 (experiment; non-PQ scans only)
+  int scan_group = 0;  // spec "scan_group": list-major MFMA scan shared
+                       // across the queries of a batch (DESIGN.md §6n;
+                       // ivfsq fp16, k <= 16). Tolerance path, off by
+                       // default
+  DevBuf grp_ws;       // its counters, tile table, pair order and A rows
 
   DevBuf centroids, cnorm, codebooks, sq_vmin, sq_vdiff, sq_scale;
   // CSR code image (slab arena; csr_rows rows grouped by list) + pending
@@ -1179,6 +1185,18 @@ static dfann_index *create_from_spec(const std::string &js) {
   } else if (json_int(js, "opq_dim", 0) != 0) {
     delete h;
     throw std::runtime_error("opq_dim given without \"opq\": 1");
+  }
+  h->scan_group = (int)json_int(js, "scan_group", 0);
+  if (h->scan_group != 0 && h->scan_group != 1) {
+    int v = h->scan_group;
+    delete h;
+    throw std::runtime_error("scan_group=" + std::to_string(v) +
+                             " unsupported (supported: 0, 1)");
+  }
+  if (h->scan_group && (h->type != T_IVFSQ || h->sq_int())) {
+    delete h;
+    throw std::runtime_error("\"scan_group\": 1 unsupported for index type '" +
+                             t + "' (ivfsq with sq_type fp16 only)");
   }
   h->rr = json_int(js, "rr", 0) != 0;
   if (h->rr && h->type != T_IVFRBQ) {
@@ -2529,6 +2547,127 @@ static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
                         float *D, int64_t *I, hipStream_t stream,
                         const uint32_t *allow);
 
+// ---------------------------------------------------------------------------
+// Grouped scan (scan_group.hip): spec "scan_group" on an ivfsq
+// fp16 index, register-path k. DFANN_SCAN_GROUP=0|1 (A/B knob, read per call)
+// overrides the spec on an index that could take the path.
+// ---------------------------------------------------------------------------
+static bool scan_group_on(const dfann_index *h, int k) {
+  if (h->type != T_IVFSQ || h->sq_int() || !use_regsel(k)) return false;
+  int on = h->scan_group;
+  if (const char *e = getenv("DFANN_SCAN_GROUP"))  // experiment override
+    on = atoi(e) != 0;
+  return on != 0;
+}
+
+template <int KP>
+static void launch_scan_grp(dim3 g, size_t lds, hipStream_t stream, bool ip,
+                            bool filt, const GrpScanArgs &a) {
+  auto kern = ip ? (filt ? k_scan_sqf_grp<KP, true, true>
+                         : k_scan_sqf_grp<KP, true, false>)
+                 : (filt ? k_scan_sqf_grp<KP, false, true>
+                         : k_scan_sqf_grp<KP, false, false>);
+  hipLaunchKernelGGL(kern, g, dim3(256), lds, stream, a);
+}
+
+// Same contract as scan_and_merge: candidates to (q * nprobe + slot) * k of
+// ws3 / ws4, then the pair-major path's own merge. Stream-ordered; the
+// workspace grows only when a shape is first seen.
+static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
+                                 int nprobe, const int32_t *probes,
+                                 const float *keys, int k, float *D,
+                                 int64_t *I, hipStream_t stream,
+                                 const uint32_t *allow) {
+  const bool ip = h->metric == M_IP;
+  const int64_t P = nq * nprobe;
+  if (P >= (1LL << 31))
+    throw std::runtime_error("scan_group: nq * nprobe must be below 2^31");
+  const int nlist = h->nlist;
+  const int ldh = h->stride / 2;  // round_up(d, 8): the stored row, zero pad
+  const int nkb = (ldh + GS_K - 1) / GS_K;
+  const int64_t tile_cap = (P + GS_TQ - 1) / GS_TQ + std::min<int64_t>(nlist, P);
+  h->ws3.ensure((size_t)P * k * 4);
+  h->ws4.ensure((size_t)P * k * 4);
+  float *cand_d = h->ws3.as<float>();
+  unsigned *cand_p = h->ws4.as<unsigned>();
+  // workspace carve: [cnt | cur | meta(4)] zeroed per call, start, order,
+  // qn, tiles (16-byte), A rows (16-byte)
+  auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t nzero = (size_t)2 * nlist + 4;
+  const size_t o_start = up16(nzero * 4);
+  const size_t o_order = o_start + up16((size_t)nlist * 4);
+  const size_t o_qn = o_order + up16((size_t)P * 4);
+  const size_t o_tiles = o_qn + up16((size_t)P * 4);
+  const size_t o_A = o_tiles + (size_t)tile_cap * 16;
+  h->grp_ws.ensure(o_A + (size_t)P * ldh * 2);
+  uint8_t *wsb = h->grp_ws.as<uint8_t>();
+  int *cnt = reinterpret_cast<int *>(wsb);
+  int *cur = cnt + nlist;
+  int *meta = cur + nlist;
+  int *start = reinterpret_cast<int *>(wsb + o_start);
+  int *order = reinterpret_cast<int *>(wsb + o_order);
+  float *qn = reinterpret_cast<float *>(wsb + o_qn);
+  int4 *tiles = reinterpret_cast<int4 *>(wsb + o_tiles);
+  unsigned short *A = reinterpret_cast<unsigned short *>(wsb + o_A);
+
+  GrpScanArgs a = {};
+  if (allow) {
+    // as scan_prepare: outside the scan timing events
+    int64_t waves = (h->csr_rows + 63) / 64;
+    h->filt_ws.ensure((size_t)waves * 8);
+    hipLaunchKernelGGL(k_filter_id2pos, dim3((unsigned)((waves + 3) / 4)),
+                       dim3(256), 0, stream, allow, h->cr_ids.as<int64_t>(),
+                       (long long)h->csr_rows, h->filt_ws.as<unsigned>());
+    a.posbits = h->filt_ws.as<unsigned>();
+  }
+  TimingEv e;
+  if (h->timing) e = h->ev_begin(stream);
+  const int64_t *off = h->cr_off.as<int64_t>();
+  const dim3 gp((unsigned)((P + 255) / 256));
+  hipLaunchKernelGGL(k_grp_zero, dim3((unsigned)((nzero + 255) / 256)),
+                     dim3(256), 0, stream, cnt, (int)nzero);
+  hipLaunchKernelGGL(k_grp_count, gp, dim3(256), 0, stream, probes, off,
+                     (long long)P, nlist, k, cnt, cand_d, cand_p);
+  hipLaunchKernelGGL(k_grp_tiles, dim3(1), dim3(256), 0, stream, cnt, nlist,
+                     start, tiles, meta);
+  hipLaunchKernelGGL(k_grp_scatter, gp, dim3(256), 0, stream, probes, off,
+                     (long long)P, nlist, start, cur, order);
+  hipLaunchKernelGGL(k_grp_operands, dim3((unsigned)((P + 3) / 4)), dim3(256),
+                     0, stream, q, h->centroids.as<float>(), probes, keys,
+                     order, meta, nprobe, h->d, ldh, ip ? 1 : 0, A, qn);
+  a.tiles = tiles;
+  a.meta = meta;
+  a.order = order;
+  a.A = A;
+  a.qn = qn;
+  // (uploads the slab table after a CSR rebuild: inside the scan events)
+  a.codes = h->csr_arena.dev_table(stream);
+  a.off = off;
+  a.ldh = ldh;
+  a.stride = h->stride;
+  a.rlog = h->csr_arena.rlog;
+  a.k = k;
+  // A tile resident in LDS across the row tiles while all its K blocks fit
+  a.a_res = (size_t)nkb * GS_A_BYTES <= GS_A_RES_MAX;
+  const size_t lds =
+      GS_A_OFF + (size_t)(a.a_res ? nkb : 2) * GS_A_BYTES;
+  a.cand_d = cand_d;
+  a.cand_p = cand_p;
+  const dim3 g((unsigned)tile_cap);
+  const bool filt = allow != nullptr;
+  if (k <= 4) launch_scan_grp<4>(g, lds, stream, ip, filt, a);
+  else if (k <= 8) launch_scan_grp<8>(g, lds, stream, ip, filt, a);
+  else launch_scan_grp<16>(g, lds, stream, ip, filt, a);
+  if (h->timing) h->ev_end(e, stream, h->ev_scan);
+  scan_account(h, nq, nprobe, probes);
+  TimingEv em;
+  if (h->timing) em = h->ev_begin(stream);
+  launch_merge_cand(stream, cand_d, cand_p, nq, nprobe * k, k,
+                    h->cr_ids.as<int64_t>(), ip, D, I, MERGE_WAVE);
+  if (h->timing) h->ev_end(em, stream, h->ev_merge);
+  HIP_CHECK(hipGetLastError());
+}
+
 static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                            int nprobe, const int32_t *probes,
                            const float *keys, int k, float *D, int64_t *I,
@@ -2536,6 +2675,11 @@ static void scan_and_merge(dfann_index *h, int64_t nq, const float *q,
                            const uint32_t *allow = nullptr) {
   if (k > K_SEL_MAX) {
     large_k_ivf(h, nq, q, nprobe, probes, keys, k, D, I, stream, allow);
+    return;
+  }
+  if (scan_group_on(h, k)) {
+    scan_group_and_merge(h, nq, q, nprobe, probes, keys, k, D, I, stream,
+                         allow);
     return;
   }
   const bool ip = h->metric == M_IP;
@@ -2947,8 +3091,9 @@ static const int64_t PIPE_CHUNK_AUTO = 2560;
 
 // Spec "pipe_lanes" / "pipe_chunk"; DFANN_PIPE_LANES / DFANN_PIPE_CHUNK (A/B
 // knobs, read per call) override them. An explicit chunk is used as given.
-// Serial whatever is asked: filtered search, the large-k path, and a call
-// with timing on (its per-stage event buckets are defined on one stream).
+// Serial whatever is asked: filtered search, the large-k path, the grouped
+// scan (it shares lists across the whole batch and has one workspace), and a
+// call with timing on (its per-stage event buckets are defined on one stream).
 static PipePlan plan_pipe(const dfann_index *h, int64_t nq, int k, int nprobe,
                           const uint32_t *allow) {
   int lanes = h->pipe_lanes;
@@ -2957,7 +3102,8 @@ static PipePlan plan_pipe(const dfann_index *h, int64_t nq, int k, int nprobe,
   int64_t chunk = h->pipe_chunk;
   if (const char *e = getenv("DFANN_PIPE_CHUNK"))  // experiment override
     chunk = atoll(e);
-  if (allow || k > K_SEL_MAX || h->timing || lanes == 0 || lanes == 1)
+  if (allow || k > K_SEL_MAX || h->timing || lanes == 0 || lanes == 1 ||
+      scan_group_on(h, k))
     return {1, nq};
   const ScanPlan sp = plan_scan(h, k, nprobe);
   if (lanes < 0) {

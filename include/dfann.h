@@ -190,6 +190,17 @@ typedef void *dfann_stream;             /* hipStream_t */
  * (dim x dim, orthonormal) in front, generated at train and handled by the
  * transform calls below exactly like an "opq" matrix with opq_dim == dim;
  * "rr" on another index type is an error naming the key.
+ * Grouped scan, "ivfsq" with "sq_type": "fp16" only:
+ * "scan_group": 0 | 1 (default 0). With 1, searches with k <= 16 (plain,
+ * filtered, preassigned, reconstruct, and the base stage under "refine" when
+ * k' <= 16) scan every probed list once per 64 of the batch's queries that
+ * probe it, on the matrix cores, instead of once per query. The query side
+ * is rounded to fp16 (L2: fp16(q - c), IP: fp16(q)), so distances are the
+ * tolerance tier of DESIGN.md §4, not the bits of "scan_group": 0; a
+ * query's result does not depend on the rest of its batch. k > 16 and range
+ * search are unchanged. Errors naming the key: a value other than 0 or 1,
+ * and 1 on any other index type or sq_type. DFANN_SCAN_GROUP=0|1 in the
+ * environment overrides the key per call on such an index.
  * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
  * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
  * together with "refine".
