@@ -16,6 +16,7 @@
 #include "kernels.hip"
 #include "hnsw.hip"
 #include "scan_group.hip"
+#include "scan_group_sq8.hip"
 
 #include <cstdio>
 #include <cstdlib>
@@ -371,7 +372,9 @@ struct dfann_index {
                        // across the queries of a batch (DESIGN.md §6n;
                        // ivfsq fp16, k <= 16). Tolerance path, off by
                        // default
-  DevBuf grp_ws;       // its counters, tile table, pair order and A rows
+  int scan_group_sq8 = 0;  // spec "scan_group_sq8": the same for 8-bit
+                           // codes, off by default
+  DevBuf grp_ws;       // their counters, tile table, pair order and A rows
 
   DevBuf centroids, cnorm, codebooks, sq_vmin, sq_vdiff, sq_scale;
   // CSR code image (slab arena; csr_rows rows grouped by list) + pending
@@ -1197,6 +1200,24 @@ static dfann_index *create_from_spec(const std::string &js) {
     delete h;
     throw std::runtime_error("\"scan_group\": 1 unsupported for index type '" +
                              t + "' (ivfsq with sq_type fp16 only)");
+  }
+  h->scan_group_sq8 = (int)json_int(js, "scan_group_sq8", 0);
+  if (h->scan_group_sq8 != 0 && h->scan_group_sq8 != 1) {
+    int v = h->scan_group_sq8;
+    delete h;
+    throw std::runtime_error("scan_group_sq8=" + std::to_string(v) +
+                             " unsupported (supported: 0, 1)");
+  }
+  if (h->scan_group_sq8 && (h->type != T_IVFSQ || h->sq_bits != 8)) {
+    delete h;
+    throw std::runtime_error(
+        "\"scan_group_sq8\": 1 unsupported for index type '" + t +
+        "' (ivfsq with sq_type 8bit only)");
+  }
+  if (h->scan_group_sq8 && gs8_lds_bytes(h->d) > GS8_LDS_MAX) {
+    delete h;
+    throw std::runtime_error("\"scan_group_sq8\": 1 unsupported for dim " +
+                             std::to_string(h->d) + " (scan LDS over budget)");
   }
   h->rr = json_int(js, "rr", 0) != 0;
   if (h->rr && h->type != T_IVFRBQ) {
@@ -2550,14 +2571,35 @@ static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
 // ---------------------------------------------------------------------------
 // Grouped scan (scan_group.hip): spec "scan_group" on an ivfsq
 // fp16 index, register-path k. DFANN_SCAN_GROUP=0|1 (A/B knob, read per call)
-// overrides the spec on an index that could take the path.
+// overrides the spec on an index that could take the path. 8-bit codes
+// (§6o, scan_group_sq8.hip) have a key and a knob of their own, "scan_group_sq8"
+// and DFANN_SCAN_GROUP_SQ8: neither pair reaches the other's indexes.
 // ---------------------------------------------------------------------------
 static bool scan_group_on(const dfann_index *h, int k) {
-  if (h->type != T_IVFSQ || h->sq_int() || !use_regsel(k)) return false;
-  int on = h->scan_group;
-  if (const char *e = getenv("DFANN_SCAN_GROUP"))  // experiment override
-    on = atoi(e) != 0;
+  if (h->type != T_IVFSQ || !use_regsel(k)) return false;
+  int on;
+  const char *e;
+  if (!h->sq_int()) {
+    on = h->scan_group;
+    e = getenv("DFANN_SCAN_GROUP");  // experiment override
+  } else if (h->sq_bits == 8 && gs8_lds_bytes(h->d) <= GS8_LDS_MAX) {
+    on = h->scan_group_sq8;
+    e = getenv("DFANN_SCAN_GROUP_SQ8");  // experiment override
+  } else {
+    return false;
+  }
+  if (e) on = atoi(e) != 0;
   return on != 0;
+}
+
+template <int KP>
+static void launch_scan_grp8(dim3 g, size_t lds, hipStream_t stream, bool ip,
+                             bool filt, const Grp8ScanArgs &a) {
+  auto kern = ip ? (filt ? k_scan_sq8_grp<KP, true, true>
+                         : k_scan_sq8_grp<KP, true, false>)
+                 : (filt ? k_scan_sq8_grp<KP, false, true>
+                         : k_scan_sq8_grp<KP, false, false>);
+  hipLaunchKernelGGL(kern, g, dim3(256), lds, stream, a);
 }
 
 template <int KP>
@@ -2583,7 +2625,10 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   if (P >= (1LL << 31))
     throw std::runtime_error("scan_group: nq * nprobe must be below 2^31");
   const int nlist = h->nlist;
-  const int ldh = h->stride / 2;  // round_up(d, 8): the stored row, zero pad
+  const bool sq8 = h->sq_bits == 8;
+  // halves of an A row: round_up(d, 8), the stored fp16 row with its zero
+  // pad, or for 8-bit codes round_up(d, 16), one half per stored byte
+  const int ldh = sq8 ? h->stride : h->stride / 2;
   const int nkb = (ldh + GS_K - 1) / GS_K;
   const int64_t tile_cap = (P + GS_TQ - 1) / GS_TQ + std::min<int64_t>(nlist, P);
   h->ws3.ensure((size_t)P * k * 4);
@@ -2591,13 +2636,14 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   float *cand_d = h->ws3.as<float>();
   unsigned *cand_p = h->ws4.as<unsigned>();
   // workspace carve: [cnt | cur | meta(4)] zeroed per call, start, order,
-  // qn, tiles (16-byte), A rows (16-byte)
+  // qn, [8-bit: 2^-e,] tiles (16-byte), A rows (16-byte)
   auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
   const size_t nzero = (size_t)2 * nlist + 4;
   const size_t o_start = up16(nzero * 4);
   const size_t o_order = o_start + up16((size_t)nlist * 4);
   const size_t o_qn = o_order + up16((size_t)P * 4);
-  const size_t o_tiles = o_qn + up16((size_t)P * 4);
+  const size_t o_inv = o_qn + up16((size_t)P * 4);
+  const size_t o_tiles = o_inv + (sq8 ? up16((size_t)P * 4) : 0);
   const size_t o_A = o_tiles + (size_t)tile_cap * 16;
   h->grp_ws.ensure(o_A + (size_t)P * ldh * 2);
   uint8_t *wsb = h->grp_ws.as<uint8_t>();
@@ -2607,6 +2653,7 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   int *start = reinterpret_cast<int *>(wsb + o_start);
   int *order = reinterpret_cast<int *>(wsb + o_order);
   float *qn = reinterpret_cast<float *>(wsb + o_qn);
+  float *inv = reinterpret_cast<float *>(wsb + o_inv);
   int4 *tiles = reinterpret_cast<int4 *>(wsb + o_tiles);
   unsigned short *A = reinterpret_cast<unsigned short *>(wsb + o_A);
 
@@ -2632,9 +2679,6 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
                      start, tiles, meta);
   hipLaunchKernelGGL(k_grp_scatter, gp, dim3(256), 0, stream, probes, off,
                      (long long)P, nlist, start, cur, order);
-  hipLaunchKernelGGL(k_grp_operands, dim3((unsigned)((P + 3) / 4)), dim3(256),
-                     0, stream, q, h->centroids.as<float>(), probes, keys,
-                     order, meta, nprobe, h->d, ldh, ip ? 1 : 0, A, qn);
   a.tiles = tiles;
   a.meta = meta;
   a.order = order;
@@ -2647,17 +2691,36 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   a.stride = h->stride;
   a.rlog = h->csr_arena.rlog;
   a.k = k;
-  // A tile resident in LDS across the row tiles while all its K blocks fit
-  a.a_res = (size_t)nkb * GS_A_BYTES <= GS_A_RES_MAX;
-  const size_t lds =
-      GS_A_OFF + (size_t)(a.a_res ? nkb : 2) * GS_A_BYTES;
   a.cand_d = cand_d;
   a.cand_p = cand_p;
   const dim3 g((unsigned)tile_cap);
   const bool filt = allow != nullptr;
-  if (k <= 4) launch_scan_grp<4>(g, lds, stream, ip, filt, a);
-  else if (k <= 8) launch_scan_grp<8>(g, lds, stream, ip, filt, a);
-  else launch_scan_grp<16>(g, lds, stream, ip, filt, a);
+  if (sq8) {
+    hipLaunchKernelGGL(k_grp_operands_sq8, dim3((unsigned)((P + 3) / 4)),
+                       dim3(256), 0, stream, q, h->centroids.as<float>(),
+                       probes, keys, order, meta, h->sq_vmin.as<float>(),
+                       h->sq_scale.as<float>(), nprobe, h->d, ldh, ip ? 1 : 0,
+                       A, qn, inv);
+    // K blocks of 128 codes, 16 KB of A each; same residency rule
+    a.a_res = (size_t)((h->d + GS8_KB - 1) / GS8_KB) * GS8_A_BYTES <=
+              GS_A_RES_MAX;
+    const Grp8ScanArgs b = {a, inv, h->sq_scale.as<float>(), h->d};
+    const size_t lds = gs8_lds_bytes(h->d);
+    if (k <= 4) launch_scan_grp8<4>(g, lds, stream, ip, filt, b);
+    else if (k <= 8) launch_scan_grp8<8>(g, lds, stream, ip, filt, b);
+    else launch_scan_grp8<16>(g, lds, stream, ip, filt, b);
+  } else {
+    hipLaunchKernelGGL(k_grp_operands, dim3((unsigned)((P + 3) / 4)),
+                       dim3(256), 0, stream, q, h->centroids.as<float>(),
+                       probes, keys, order, meta, nprobe, h->d, ldh,
+                       ip ? 1 : 0, A, qn);
+    // A tile resident in LDS across the row tiles while all its K blocks fit
+    a.a_res = (size_t)nkb * GS_A_BYTES <= GS_A_RES_MAX;
+    const size_t lds = GS_A_OFF + (size_t)(a.a_res ? nkb : 2) * GS_A_BYTES;
+    if (k <= 4) launch_scan_grp<4>(g, lds, stream, ip, filt, a);
+    else if (k <= 8) launch_scan_grp<8>(g, lds, stream, ip, filt, a);
+    else launch_scan_grp<16>(g, lds, stream, ip, filt, a);
+  }
   if (h->timing) h->ev_end(e, stream, h->ev_scan);
   scan_account(h, nq, nprobe, probes);
   TimingEv em;

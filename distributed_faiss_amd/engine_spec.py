@@ -247,6 +247,7 @@ ENGINE_PERF_KNOBS = (
     "pq_lut_f16",     # fp16 ADC tables (tolerance path)
     "scan_fan",       # list-segment fan (experiment knob)
     "scan_group",     # list-major MFMA scan, ivfsq fp16 (tolerance path)
+    "scan_group_sq8", # list-major MFMA scan, ivfsq 8bit (tolerance path)
     "range_max_results",  # range search: largest result, in hits
     "k_max",          # largest k served, 512..2048 (large-k path above 512)
     "pipe_lanes",     # IVF search pipeline: stream lanes (-1 auto, 1 serial)

@@ -201,6 +201,14 @@ typedef void *dfann_stream;             /* hipStream_t */
  * search are unchanged. Errors naming the key: a value other than 0 or 1,
  * and 1 on any other index type or sq_type. DFANN_SCAN_GROUP=0|1 in the
  * environment overrides the key per call on such an index.
+ * Grouped scan of 8-bit lists, "ivfsq" with "sq_type": "8bit" only (DESIGN.md
+ * §6o): "scan_group_sq8": 0 | 1 (default 0), the same envelope as
+ * "scan_group". The stored bytes enter the matrix cores exactly (as c - 128);
+ * the query side, (q - c - mid) * scale (L2) or q * scale (IP) with a
+ * per-query power-of-two scale, is rounded to fp16 once: tolerance tier, not
+ * the bits of "scan_group_sq8": 0. Errors naming the key: a value other than
+ * 0 or 1, 1 on any other index type or sq_type, and 1 with dim above 24448.
+ * DFANN_SCAN_GROUP_SQ8=0|1 overrides the key per call on such an index.
  * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
  * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
  * together with "refine".
