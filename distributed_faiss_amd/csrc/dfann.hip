@@ -17,6 +17,7 @@
 #include "hnsw.hip"
 #include "scan_group.hip"
 #include "scan_group_sq8.hip"
+#include "scan_group_pq.hip"
 
 #include <cstdio>
 #include <cstdlib>
@@ -374,7 +375,13 @@ struct dfann_index {
                        // default
   int scan_group_sq8 = 0;  // spec "scan_group_sq8": the same for 8-bit
                            // codes, off by default
+  int scan_group_pq = 0;  // spec "scan_group_pq": the same for ivfpq lists
+                          // with 8-bit codes, decoded through cb16 on the
+                          // way to LDS, off by default
   DevBuf grp_ws;       // their counters, tile table, pair order and A rows
+  DevBuf cb16;  // scan_group_pq: fp16(codebooks * 2^ec), then the int ec;
+                // derived (refresh_cb16), never saved
+  bool cb16_ok = false;  // cb16 matches the codebooks
 
   DevBuf centroids, cnorm, codebooks, sq_vmin, sq_vdiff, sq_scale;
   // CSR code image (slab arena; csr_rows rows grouped by list) + pending
@@ -492,6 +499,11 @@ struct dfann_index {
 // ---------------------------------------------------------------------------
 
 static bool use_regsel(int k) { return k <= 16; }
+// shapes k_scan_pq_grp serves
+static bool gsp_shape_ok(const dfann_index *h) {
+  return h->nbits == 8 && h->dsub % 2 == 0 && !h->pq_pre &&
+         gsp_lds_bytes(h->d, h->stride) <= GSP_LDS_MAX;
+}
 // k cap of the Sel-buffer kernels (SEL_CAP / 2); above it, up to the index's
 // k_max <= SEG_KMAX, k_select_seg
 static const int K_SEL_MAX = 512;
@@ -621,8 +633,21 @@ static void gemm_keys(dfann_index *h, const float *A, int64_t Mrows,
   gemm_keys_b(h, A, Mrows, B, nullptr, N, K, bn, qn, mode, keys, stream);
 }
 
+// The grouped PQ scan's codebook image. Built with the
+// codebooks on an index that has the key; an index that reaches the path
+// through DFANN_SCAN_GROUP_PQ alone builds it in its first such search.
+static void refresh_cb16(dfann_index *h, hipStream_t stream) {
+  const size_t o_ec = gsp_cb16_ec_off(h->d);
+  h->cb16.ensure(o_ec + 16);
+  hipLaunchKernelGGL(k_pq_cb16, dim3(1), dim3(1024), 0, stream,
+                     h->codebooks.as<float>(), (long long)h->d * 256,
+                     h->cb16.as<unsigned short>(),
+                     reinterpret_cast<int *>(h->cb16.as<uint8_t>() + o_ec));
+  h->cb16_ok = true;
+}
+
 // refresh derived images after (re)training / loading: bf16 centroids,
-// PQ-L2 precomputed term2
+// PQ-L2 precomputed term2, the grouped PQ scan's fp16 codebooks
 static void refresh_cent_bf16(dfann_index *h, hipStream_t stream) {
   if (h->coarse_bf16 && h->centroids.p) {
     h->cent_bf16.ensure((size_t)h->nlist * h->d * 2);
@@ -639,6 +664,8 @@ static void refresh_cent_bf16(dfann_index *h, hipStream_t stream) {
                        h->codebooks.as<float>(), h->nlist, h->m, h->dsub,
                        h->term2.as<float>());
   }
+  h->cb16_ok = false;
+  if (h->scan_group_pq && h->codebooks.p) refresh_cb16(h, stream);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1219,6 +1246,25 @@ static dfann_index *create_from_spec(const std::string &js) {
     throw std::runtime_error("\"scan_group_sq8\": 1 unsupported for dim " +
                              std::to_string(h->d) + " (scan LDS over budget)");
   }
+  h->scan_group_pq = (int)json_int(js, "scan_group_pq", 0);
+  if (h->scan_group_pq != 0 && h->scan_group_pq != 1) {
+    int v = h->scan_group_pq;
+    delete h;
+    throw std::runtime_error("scan_group_pq=" + std::to_string(v) +
+                             " unsupported (supported: 0, 1)");
+  }
+  if (h->scan_group_pq && (h->type != T_IVFPQ || h->nbits != 8)) {
+    delete h;
+    throw std::runtime_error(
+        "\"scan_group_pq\": 1 unsupported for index type '" + t +
+        "' (ivfpq with nbits 8 only)");
+  }
+  if (h->scan_group_pq && h->pq_pre) {
+    delete h;
+    throw std::runtime_error(
+        "\"scan_group_pq\": 1 with pq_precomputed unsupported (the term "
+        "tables have no role on the grouped path)");
+  }
   h->rr = json_int(js, "rr", 0) != 0;
   if (h->rr && h->type != T_IVFRBQ) {
     delete h;
@@ -1334,6 +1380,21 @@ static dfann_index *create_from_spec(const std::string &js) {
     h->trained = true;  // flat needs no training
   }
   h->stride = round16(h->code_bytes);
+  if (h->scan_group_pq) {
+    std::string bad;
+    if (h->dsub % 2)
+      bad = "odd dsub=" + std::to_string(h->dsub) +
+            " (dim / m must be even: codewords are gathered two halves at "
+            "a time)";
+    else if (!gsp_shape_ok(h))
+      bad = "dim=" + std::to_string(h->d) + ", m=" + std::to_string(h->m) +
+            " (scan LDS " + std::to_string(gsp_lds_bytes(h->d, h->stride)) +
+            " bytes, limit " + std::to_string(GSP_LDS_MAX) + ")";
+    if (!bad.empty()) {
+      delete h;
+      throw std::runtime_error("\"scan_group_pq\": 1 unsupported for " + bad);
+    }
+  }
   h->merge_mb = (int)json_int(js, "merge_mb", 2048);
   if (h->merge_mb < 1) h->merge_mb = 1;
   // 64 MB slabs: small enough that an empty index costs little, large
@@ -2573,13 +2634,20 @@ static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
 // fp16 index, register-path k. DFANN_SCAN_GROUP=0|1 (A/B knob, read per call)
 // overrides the spec on an index that could take the path. 8-bit codes
 // (§6o, scan_group_sq8.hip) have a key and a knob of their own, "scan_group_sq8"
-// and DFANN_SCAN_GROUP_SQ8: neither pair reaches the other's indexes.
+// and DFANN_SCAN_GROUP_SQ8, ivfpq lists with 8-bit codes (§6p,
+// scan_group_pq.hip) "scan_group_pq" and DFANN_SCAN_GROUP_PQ: no pair reaches
+// another's indexes.
 // ---------------------------------------------------------------------------
 static bool scan_group_on(const dfann_index *h, int k) {
-  if (h->type != T_IVFSQ || !use_regsel(k)) return false;
+  if ((h->type != T_IVFSQ && h->type != T_IVFPQ) || !use_regsel(k))
+    return false;
   int on;
   const char *e;
-  if (!h->sq_int()) {
+  if (h->type == T_IVFPQ) {
+    if (!gsp_shape_ok(h)) return false;
+    on = h->scan_group_pq;
+    e = getenv("DFANN_SCAN_GROUP_PQ");  // experiment override
+  } else if (!h->sq_int()) {
     on = h->scan_group;
     e = getenv("DFANN_SCAN_GROUP");  // experiment override
   } else if (h->sq_bits == 8 && gs8_lds_bytes(h->d) <= GS8_LDS_MAX) {
@@ -2600,6 +2668,26 @@ static void launch_scan_grp8(dim3 g, size_t lds, hipStream_t stream, bool ip,
                  : (filt ? k_scan_sq8_grp<KP, false, true>
                          : k_scan_sq8_grp<KP, false, false>);
   hipLaunchKernelGGL(kern, g, dim3(256), lds, stream, a);
+}
+
+template <int KP, int V>
+static void launch_scan_grp_pq_v(dim3 g, size_t lds, hipStream_t stream,
+                                 bool ip, bool filt, const GrpPqScanArgs &a) {
+  auto kern = ip ? (filt ? k_scan_pq_grp<KP, true, true, V>
+                         : k_scan_pq_grp<KP, true, false, V>)
+                 : (filt ? k_scan_pq_grp<KP, false, true, V>
+                         : k_scan_pq_grp<KP, false, false, V>);
+  hipLaunchKernelGGL(kern, g, dim3(256), lds, stream, a);
+}
+
+// V: the largest of 8, 4, 2 that divides dsub (even by the create check)
+template <int KP>
+static void launch_scan_grp_pq(dim3 g, size_t lds, hipStream_t stream, bool ip,
+                               bool filt, const GrpPqScanArgs &a) {
+  if (a.dsub % 8 == 0) launch_scan_grp_pq_v<KP, 8>(g, lds, stream, ip, filt, a);
+  else if (a.dsub % 4 == 0)
+    launch_scan_grp_pq_v<KP, 4>(g, lds, stream, ip, filt, a);
+  else launch_scan_grp_pq_v<KP, 2>(g, lds, stream, ip, filt, a);
 }
 
 template <int KP>
@@ -2625,10 +2713,12 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   if (P >= (1LL << 31))
     throw std::runtime_error("scan_group: nq * nprobe must be below 2^31");
   const int nlist = h->nlist;
-  const bool sq8 = h->sq_bits == 8;
+  const bool pq = h->type == T_IVFPQ;
+  const bool sq8 = !pq && h->sq_bits == 8;
   // halves of an A row: round_up(d, 8), the stored fp16 row with its zero
-  // pad, or for 8-bit codes round_up(d, 16), one half per stored byte
-  const int ldh = sq8 ? h->stride : h->stride / 2;
+  // pad (the same for PQ, whose B rows are decoded), or for 8-bit codes
+  // round_up(d, 16), one half per stored byte
+  const int ldh = pq ? (h->d + 7) & ~7 : sq8 ? h->stride : h->stride / 2;
   const int nkb = (ldh + GS_K - 1) / GS_K;
   const int64_t tile_cap = (P + GS_TQ - 1) / GS_TQ + std::min<int64_t>(nlist, P);
   h->ws3.ensure((size_t)P * k * 4);
@@ -2636,14 +2726,15 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   float *cand_d = h->ws3.as<float>();
   unsigned *cand_p = h->ws4.as<unsigned>();
   // workspace carve: [cnt | cur | meta(4)] zeroed per call, start, order,
-  // qn, [8-bit: 2^-e,] tiles (16-byte), A rows (16-byte)
+  // qn, [8-bit and PQ: the slot's inverse scale,] tiles (16-byte), A rows
+  // (16-byte)
   auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
   const size_t nzero = (size_t)2 * nlist + 4;
   const size_t o_start = up16(nzero * 4);
   const size_t o_order = o_start + up16((size_t)nlist * 4);
   const size_t o_qn = o_order + up16((size_t)P * 4);
   const size_t o_inv = o_qn + up16((size_t)P * 4);
-  const size_t o_tiles = o_inv + (sq8 ? up16((size_t)P * 4) : 0);
+  const size_t o_tiles = o_inv + (sq8 || pq ? up16((size_t)P * 4) : 0);
   const size_t o_A = o_tiles + (size_t)tile_cap * 16;
   h->grp_ws.ensure(o_A + (size_t)P * ldh * 2);
   uint8_t *wsb = h->grp_ws.as<uint8_t>();
@@ -2695,7 +2786,22 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   a.cand_p = cand_p;
   const dim3 g((unsigned)tile_cap);
   const bool filt = allow != nullptr;
-  if (sq8) {
+  if (pq) {
+    if (!h->cb16_ok) refresh_cb16(h, stream);
+    const int *ec =reinterpret_cast<const int *>(h->cb16.as<uint8_t>() +
+                                                  gsp_cb16_ec_off(h->d));
+    hipLaunchKernelGGL(k_grp_operands_pq, dim3((unsigned)((P + 3) / 4)),
+                       dim3(256), 0, stream, q, h->centroids.as<float>(),
+                       probes, keys, order, meta, ec, nprobe, h->d, ldh,
+                       ip ? 1 : 0, A, qn, inv);
+    a.a_res = (size_t)nkb * GS_A_BYTES <= GS_A_RES_MAX;
+    const GrpPqScanArgs b = {a, inv, h->cb16.as<unsigned short>(), ec, h->d,
+                             h->dsub};
+    const size_t lds = gsp_lds_bytes(h->d, h->stride);
+    if (k <= 4) launch_scan_grp_pq<4>(g, lds, stream, ip, filt, b);
+    else if (k <= 8) launch_scan_grp_pq<8>(g, lds, stream, ip, filt, b);
+    else launch_scan_grp_pq<16>(g, lds, stream, ip, filt, b);
+  } else if (sq8) {
     hipLaunchKernelGGL(k_grp_operands_sq8, dim3((unsigned)((P + 3) / 4)),
                        dim3(256), 0, stream, q, h->centroids.as<float>(),
                        probes, keys, order, meta, h->sq_vmin.as<float>(),

@@ -209,6 +209,17 @@ typedef void *dfann_stream;             /* hipStream_t */
  * the bits of "scan_group_sq8": 0. Errors naming the key: a value other than
  * 0 or 1, 1 on any other index type or sq_type, and 1 with dim above 24448.
  * DFANN_SCAN_GROUP_SQ8=0|1 overrides the key per call on such an index.
+ * Grouped scan of PQ lists, "ivfpq" with "nbits": 8 only, "opq" included
+ * (DESIGN.md §6p): "scan_group_pq": 0 | 1 (default 0), the same envelope as
+ * "scan_group". The list rows are decoded through an fp16 image of the
+ * codebooks (one power-of-two scale for the index) on their way to the matrix
+ * cores, the query side (q - c for L2, q for IP, with a per-query
+ * power-of-two scale) is rounded to fp16 once; no per-query distance table is
+ * built: tolerance tier, not the bits of "scan_group_pq": 0. Errors naming the
+ * key: a value other than 0 or 1, 1 on any other index type, with "nbits": 4,
+ * with an odd dim / m (opq_dim / m), together with "pq_precomputed", and on a
+ * shape whose scan needs more than 160 KB of LDS. DFANN_SCAN_GROUP_PQ=0|1
+ * overrides the key per call on an index that create would have accepted.
  * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
  * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
  * together with "refine".
