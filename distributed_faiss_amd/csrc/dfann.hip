@@ -18,6 +18,7 @@
 #include "scan_group.hip"
 #include "scan_group_sq8.hip"
 #include "scan_group_pq.hip"
+#include "scan_group_flat.hip"
 
 #include <cstdio>
 #include <cstdlib>
@@ -378,6 +379,9 @@ struct dfann_index {
   int scan_group_pq = 0;  // spec "scan_group_pq": the same for ivfpq lists
                           // with 8-bit codes, decoded through cb16 on the
                           // way to LDS, off by default
+  int scan_group_flat = 0;  // spec "scan_group_flat": the same for ivf_flat
+                            // lists, fp32 rows split into bf16 hi + lo on
+                            // the way to LDS, off by default
   DevBuf grp_ws;       // their counters, tile table, pair order and A rows
   DevBuf cb16;  // scan_group_pq: fp16(codebooks * 2^ec), then the int ec;
                 // derived (refresh_cb16), never saved
@@ -1264,6 +1268,24 @@ static dfann_index *create_from_spec(const std::string &js) {
     throw std::runtime_error(
         "\"scan_group_pq\": 1 with pq_precomputed unsupported (the term "
         "tables have no role on the grouped path)");
+  }
+  h->scan_group_flat = (int)json_int(js, "scan_group_flat", 0);
+  if (h->scan_group_flat != 0 && h->scan_group_flat != 1) {
+    int v = h->scan_group_flat;
+    delete h;
+    throw std::runtime_error("scan_group_flat=" + std::to_string(v) +
+                             " unsupported (supported: 0, 1)");
+  }
+  if (h->scan_group_flat && h->type != T_IVFFLAT) {
+    delete h;
+    throw std::runtime_error(
+        "\"scan_group_flat\": 1 unsupported for index type '" + t +
+        "' (ivf_flat only)");
+  }
+  if (h->scan_group_flat && gf_lds_bytes(h->d) > GF_LDS_MAX) {
+    delete h;
+    throw std::runtime_error("\"scan_group_flat\": 1 unsupported for dim " +
+                             std::to_string(h->d) + " (scan LDS over budget)");
   }
   h->rr = json_int(js, "rr", 0) != 0;
   if (h->rr && h->type != T_IVFRBQ) {
@@ -2635,15 +2657,21 @@ static void large_k_ivf(dfann_index *h, int64_t nq, const float *q, int nprobe,
 // overrides the spec on an index that could take the path. 8-bit codes
 // (§6o, scan_group_sq8.hip) have a key and a knob of their own, "scan_group_sq8"
 // and DFANN_SCAN_GROUP_SQ8, ivfpq lists with 8-bit codes (§6p,
-// scan_group_pq.hip) "scan_group_pq" and DFANN_SCAN_GROUP_PQ: no pair reaches
-// another's indexes.
+// scan_group_pq.hip) "scan_group_pq" and DFANN_SCAN_GROUP_PQ, ivf_flat lists
+// (§6q, scan_group_flat.hip) "scan_group_flat" and DFANN_SCAN_GROUP_FLAT: no
+// pair reaches another's indexes.
 // ---------------------------------------------------------------------------
 static bool scan_group_on(const dfann_index *h, int k) {
-  if ((h->type != T_IVFSQ && h->type != T_IVFPQ) || !use_regsel(k))
+  if ((h->type != T_IVFSQ && h->type != T_IVFPQ && h->type != T_IVFFLAT) ||
+      !use_regsel(k))
     return false;
   int on;
   const char *e;
-  if (h->type == T_IVFPQ) {
+  if (h->type == T_IVFFLAT) {
+    if (gf_lds_bytes(h->d) > GF_LDS_MAX) return false;
+    on = h->scan_group_flat;
+    e = getenv("DFANN_SCAN_GROUP_FLAT");  // experiment override
+  } else if (h->type == T_IVFPQ) {
     if (!gsp_shape_ok(h)) return false;
     on = h->scan_group_pq;
     e = getenv("DFANN_SCAN_GROUP_PQ");  // experiment override
@@ -2691,6 +2719,16 @@ static void launch_scan_grp_pq(dim3 g, size_t lds, hipStream_t stream, bool ip,
 }
 
 template <int KP>
+static void launch_scan_grp_flat(dim3 g, size_t lds, hipStream_t stream,
+                                 bool ip, bool filt, const GrpFlatScanArgs &a) {
+  auto kern = ip ? (filt ? k_scan_flat_grp<KP, true, true>
+                         : k_scan_flat_grp<KP, true, false>)
+                 : (filt ? k_scan_flat_grp<KP, false, true>
+                         : k_scan_flat_grp<KP, false, false>);
+  hipLaunchKernelGGL(kern, g, dim3(256), lds, stream, a);
+}
+
+template <int KP>
 static void launch_scan_grp(dim3 g, size_t lds, hipStream_t stream, bool ip,
                             bool filt, const GrpScanArgs &a) {
   auto kern = ip ? (filt ? k_scan_sqf_grp<KP, true, true>
@@ -2713,12 +2751,16 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   if (P >= (1LL << 31))
     throw std::runtime_error("scan_group: nq * nprobe must be below 2^31");
   const int nlist = h->nlist;
-  const bool pq = h->type == T_IVFPQ;
-  const bool sq8 = !pq && h->sq_bits == 8;
+  const bool pq = h->type == T_IVFPQ, flat = h->type == T_IVFFLAT;
+  const bool sq8 = !pq && !flat && h->sq_bits == 8;
   // halves of an A row: round_up(d, 8), the stored fp16 row with its zero
-  // pad (the same for PQ, whose B rows are decoded), or for 8-bit codes
-  // round_up(d, 16), one half per stored byte
-  const int ldh = pq ? (h->d + 7) & ~7 : sq8 ? h->stride : h->stride / 2;
+  // pad (the same for PQ, whose B rows are decoded), for 8-bit codes
+  // round_up(d, 16), one half per stored byte, or for ivf_flat 2 round_up(d,
+  // 32), a bf16 hi and a lo half per dimension
+  const int ldh = flat ? 2 * gf_ld(h->d)
+                  : pq ? (h->d + 7) & ~7
+                  : sq8 ? h->stride
+                        : h->stride / 2;
   const int nkb = (ldh + GS_K - 1) / GS_K;
   const int64_t tile_cap = (P + GS_TQ - 1) / GS_TQ + std::min<int64_t>(nlist, P);
   h->ws3.ensure((size_t)P * k * 4);
@@ -2786,7 +2828,18 @@ static void scan_group_and_merge(dfann_index *h, int64_t nq, const float *q,
   a.cand_p = cand_p;
   const dim3 g((unsigned)tile_cap);
   const bool filt = allow != nullptr;
-  if (pq) {
+  if (flat) {
+    hipLaunchKernelGGL(k_grp_operands_flat, dim3((unsigned)((P + 3) / 4)),
+                       dim3(256), 0, stream, q, h->centroids.as<float>(),
+                       probes, order, meta, nprobe, h->d, ldh / 2, ip ? 1 : 0,
+                       A, qn);
+    a.a_res = (size_t)nkb * GS_A_BYTES <= GS_A_RES_MAX;
+    const GrpFlatScanArgs b = {a, h->centroids.as<float>(), h->d};
+    const size_t lds = gf_lds_bytes(h->d);
+    if (k <= 4) launch_scan_grp_flat<4>(g, lds, stream, ip, filt, b);
+    else if (k <= 8) launch_scan_grp_flat<8>(g, lds, stream, ip, filt, b);
+    else launch_scan_grp_flat<16>(g, lds, stream, ip, filt, b);
+  } else if (pq) {
     if (!h->cb16_ok) refresh_cb16(h, stream);
     const int *ec =reinterpret_cast<const int *>(h->cb16.as<uint8_t>() +
                                                   gsp_cb16_ec_off(h->d));

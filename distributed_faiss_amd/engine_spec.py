@@ -249,6 +249,7 @@ ENGINE_PERF_KNOBS = (
     "scan_group",     # list-major MFMA scan, ivfsq fp16 (tolerance path)
     "scan_group_sq8", # list-major MFMA scan, ivfsq 8bit (tolerance path)
     "scan_group_pq",  # list-major MFMA scan, ivfpq nbits 8 (tolerance path)
+    "scan_group_flat",  # list-major MFMA scan, ivf_flat (split bf16, fp32 tier)
     "range_max_results",  # range search: largest result, in hits
     "k_max",          # largest k served, 512..2048 (large-k path above 512)
     "pipe_lanes",     # IVF search pipeline: stream lanes (-1 auto, 1 serial)

@@ -220,6 +220,15 @@ typedef void *dfann_stream;             /* hipStream_t */
  * with an odd dim / m (opq_dim / m), together with "pq_precomputed", and on a
  * shape whose scan needs more than 160 KB of LDS. DFANN_SCAN_GROUP_PQ=0|1
  * overrides the key per call on an index that create would have accepted.
+ * Grouped scan of fp32 lists, "ivf_flat" only:
+ * "scan_group_flat": 0 | 1 (default 0), the same envelope as "scan_group".
+ * Both operands (q - c and x - c for L2, q and x for IP) are split into a
+ * bf16 high and a bf16 low part and every dot product is three bf16 matrix
+ * products accumulated in fp32: about 2^-14 relative per product, inside the
+ * engine's fp32 tolerance, but not the bits of "scan_group_flat": 0. Errors
+ * naming the key: a value other than 0 or 1, 1 on any other index type, and 1
+ * with a dim whose scan needs more than 160 KB of LDS (above ~28000).
+ * DFANN_SCAN_GROUP_FLAT=0|1 overrides the key per call on an "ivf_flat" index.
  * Large k: "k_max": 512..2048 (default 512, see Limits). Errors naming the
  * key: a value outside that range, k_max > 512 on "hnswsq" and k_max > 512
  * together with "refine".
